@@ -12,7 +12,14 @@ value = env-steps/s of the WHOLE job (all ranks, rollout + update time).
 Default workload: 65,536 10x10 mazes per GPU (BASELINE configs[2] scale, the
 north-star's 1M env-steps/s target) running configs[1]'s rollout+update loop.
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]
+A plain run sets up, warms up, times ``--steps`` iterations and prints the
+result line.  ``--full`` adds what takes runs of its own: the CPU baseline
+(``cpu_baseline``) and, when the rollout is a graph replay, the instrumented
+rollout behind ``roofline``.  ``--dump-outputs DIR`` writes what the last timed
+iteration computed (rollout buffers, update history, parameters) as
+``DIR/<name>.npy``.
+
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 import argparse
@@ -217,6 +224,28 @@ def _workload_label(n, size, dtype):
     return f"{loop} over {n} parallel {size}x{size} 2-agent mazes per GPU ({tag})"
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per array (4 MiB of float32); 12 arrays stay well under 64 MB
+
+
+def dump_outputs(out_dir, agent, hist):
+    """What the last timed iteration handed its caller, as float32 ``<name>.npy``: the rollout's
+    buffers (rollout()'s dict), the update's per-minibatch history [K, 4] and the parameters after
+    it.  An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of that many:
+    the flat indices come from numpy's default_rng(0) and depend only on the array's size, so two
+    builds run with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    b = agent._bufs
+    arrays = {k: b[k] for k in ("obs", "masks", "act", "logp", "val", "last_val", "rew", "done", "adv", "rtg")}
+    arrays["update_hist"] = hist
+    arrays["params"] = agent.flat.data
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_MAX_ELEMS)
+            flat = flat[torch.as_tensor(idx, device=flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,14 +261,20 @@ def main():
     ap.add_argument("--size", type=int, default=10, help="default_size (cells); layout is 2*size-1")
     ap.add_argument("--horizon", type=int, default=16, help="env-steps per maze per iteration")
     ap.add_argument("--max-t", type=int, default=1200, help="max_timestep (main.py:20)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (cpu_baseline) and, with a "
+                         "graph-replayed rollout, the instrumented rollout behind the roofline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed as DIR/<name>.npy (float32; large arrays "
+                         "as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-parity", action="store_true",
                     help="parity_mode=False: every feature embedding reads its own observation slice (not the "
                          "reference's quirk Q1, under which the actor sees only obs[0:4])")
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="replay the rollout as a captured HIP graph (auto: on below 16,384 mazes per GPU, where the "
                          "per-step launches are host-bound); the env-step kernel's duration for the roofline then "
-                         "comes from one instrumented uncaptured rollout after the timed region")
+                         "comes from one instrumented uncaptured rollout after the timed region (--full)")
     a = ap.parse_args()
 
     # MARLMAZE_DP_BACKEND=gloo rehearses N ranks on fewer GPUs (ranks share devices round-robin);
@@ -276,6 +311,7 @@ def main():
     if not graph:
         agent.step_events = []  # instrumented env steps inside the timed region (uncaptured rollout)
     upd_ev, roll_ev = [], []
+    hist = None  # the last timed update's per-minibatch history (--dump-outputs)
     t0 = time.time()
     for _ in range(a.steps):
         r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -286,8 +322,8 @@ def main():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         B = T * n
-        agent.update(b["obs"][:T].reshape(B, 2, 65), b["act"].reshape(B, 2, 2), b["logp"].reshape(B),
-                     b["masks"][:T].reshape(B, 2, 6), b["adv"].reshape(B), b["val"].reshape(B))
+        hist = agent.update(b["obs"][:T].reshape(B, 2, 65), b["act"].reshape(B, 2, 2), b["logp"].reshape(B),
+                            b["masks"][:T].reshape(B, 2, 6), b["adv"].reshape(B), b["val"].reshape(B))
         e1.record()
         upd_ev.append((e0, e1))
         agent._carry_over()
@@ -299,19 +335,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    if graph:  # one instrumented uncaptured rollout after the timed region, for the env-step kernel's duration
+    if a.dump_outputs and dp.rank == 0 and a.steps > 0:
+        # the buffers as the last timed iteration left them (row 0 of obs / masks already holds the carry-over of
+        # row T), before anything below runs another rollout
+        dump_outputs(a.dump_outputs, agent, hist)
+
+    if graph and a.full:  # one instrumented uncaptured rollout after the timed region, for the env-step kernel's time
         agent.step_events = []
         agent.rollout()
         agent._carry_over()
         torch.cuda.synchronize()
-    step_ms = [s.elapsed_time(e) for s, e in agent.step_events]
+    # the env-step kernel's stamps: from the timed region (stream launches), or from --full's instrumented rollout
+    # (graph replay); a plain graph-replay run has none, and no roofline figure
+    step_ms = [s.elapsed_time(e) for s, e in agent.step_events or []]
     upd_ms = [s.elapsed_time(e) for s, e in upd_ev]
     roll_ms = [s.elapsed_time(e) for s, e in roll_ev]
-    env_step_ms = float(np.mean(step_ms))
     H = 2 * a.size - 1
     alg_bytes = H * H + 703  # layout + marks + agents r/w + maze r/w + actions + obs + masks + reward + done
-    achieved = n * alg_bytes / (env_step_ms * 1e-3) / 1e9
-    n_updates = len(agent.history) or None
     minibatches_per_iter = agent.updates_per_batch * len(range(0, batch_global // world, (batch_global // world) // 5))
     total_steps = world * n * T * a.steps
 
@@ -323,6 +363,17 @@ def main():
         with open(pmcs[-1]) as f:
             traffic = json.load(f).get("hbm_bytes_per_launch")
         traffic_src = os.path.relpath(pmcs[-1], REPO)
+    roofline = None
+    if step_ms:
+        env_step_ms = float(np.mean(step_ms))
+        achieved = n * alg_bytes / (env_step_ms * 1e-3) / 1e9
+        roofline = {
+            "kernel": "k_step (mm_env_step)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+            "alg_bytes_per_env_step": alg_bytes, "launch_us": env_step_ms * 1e3,
+            "launch_us_median": float(np.median(step_ms)) * 1e3, "launches": len(step_ms),
+            "timed_in": "the timed region" if not graph else "one instrumented rollout after the timed region",
+        }
 
     line = {
         "metric": "env-steps/sec (2-agent 10x10 maze) + PPO updates/sec",
@@ -352,17 +403,10 @@ def main():
         "rollout_env_steps_per_sec": total_steps / (elapsed - sum(upd_ms) * 1e-3),
         "rollout_ms_per_iter": float(np.mean(roll_ms)),  # GPU time of rollout() + GAE (events around it)
         "rollout_us_per_step": float(np.mean(roll_ms)) * 1e3 / T,
-        "roofline": {
-            "kernel": "k_step (mm_env_step)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-            "alg_bytes_per_env_step": alg_bytes, "launch_us": env_step_ms * 1e3,
-            "launch_us_median": float(np.median(step_ms)) * 1e3, "launches": len(step_ms),
-            "timed_in": "the timed region" if not graph else "one instrumented rollout after the timed region",
-        },
+        "roofline": roofline,  # None: graph-replayed rollout without --full
     }
-    del n_updates
     if dp.rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dp.active:

@@ -244,6 +244,44 @@ def test_global_advantage_statistics(world):
     assert torch.allclose(m, x.mean()) and torch.allclose(s, x.std())
 
 
+def test_bench_dump_outputs_writes_fixed_float32_arrays(tmp_path):
+    """bench.py --dump-outputs: every array is written as float32 under its name, small ones whole and
+    large ones as the same seeded sample on every call (the indices depend on the size alone)."""
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    T, n = 3, 5
+    g = torch.Generator().manual_seed(0)
+    big = bench.DUMP_MAX_ELEMS + 1001
+    bufs = dict(obs=torch.rand(big, generator=g), masks=torch.randint(0, 2, (T + 1, n, 2, 6), dtype=torch.uint8),
+                act=torch.randint(0, 5, (T, n, 2, 2), dtype=torch.int8), last_val=torch.rand(n, generator=g))
+    for k in ("logp", "val", "rew", "adv", "rtg"):
+        bufs[k] = torch.rand(T, n, generator=g)
+    bufs["done"] = torch.randint(0, 2, (T, n), dtype=torch.uint8)
+    agent = types.SimpleNamespace(_bufs=bufs, horizon=T, flat=types.SimpleNamespace(data=torch.rand(77, generator=g)))
+    hist = torch.rand(25, 4, generator=g)
+    out = [tmp_path / "a", tmp_path / "b"]
+    for d in out:
+        bench.dump_outputs(str(d), agent, hist)
+    names = sorted(p.name for p in out[0].iterdir())
+    assert names == sorted(k + ".npy" for k in list(bufs) + ["update_hist", "params"])
+    total = 0
+    for name in names:
+        x, y = np.load(out[0] / name), np.load(out[1] / name)
+        assert x.dtype == np.float32 and x.ndim == 1 and np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64e6
+    assert np.array_equal(np.load(out[0] / "act.npy"), bufs["act"].reshape(-1).float().numpy())
+    assert np.array_equal(np.load(out[0] / "update_hist.npy"), hist.reshape(-1).numpy())
+    obs = np.load(out[0] / "obs.npy")
+    idx = np.random.default_rng(0).integers(0, big, size=bench.DUMP_MAX_ELEMS)
+    assert np.array_equal(obs, bufs["obs"].numpy()[idx])
+
+
 def test_bench_bounded_cpu_sample_reports_progress():
     """bench.py's os.cpu_count()-thread CPU leg (_cpu_epoch_bounded): a finished
     child extrapolates its rollout chunks and one update pass to the epoch; a

@@ -5,7 +5,7 @@
 # Every step writes under gpurun_out/TAG/ and runs under its own time limit; the first failing step ends the
 # pass (no GPU step runs after a failure, a fault or a time limit).  Steps:
 #   tests            every GPU test                       tests=EXPR  the GPU tests matching -k EXPR
-#   bench            the headline line (configs[2]: 65,536 10x10 mazes, CPU baseline included)
+#   bench            the headline line (configs[2]: 65,536 10x10 mazes, CPU baseline included: bench.py --full)
 #   config1          configs[1]: 4,096 mazes, horizon 32   config3  configs[3]'s per-GPU share: 8,192 20x20 mazes
 #   f16              configs[4]'s per-GPU share: 32,768 mazes, fp16 actor/critic
 #   prof             rocprofv3 kernel trace + stats of a short headline run, the k_step timed summary and the
@@ -33,10 +33,10 @@ for s in "$@"; do
         -k "${s#tests=}" > $R/pytest_sel.log 2>&1 || fail "$s" $? $R/pytest_sel.log
       grep -E "PASSED|FAILED|^trunk3|^f16|passed|failed" $R/pytest_sel.log | tail -60 ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $R/bench.log 2>&1 || fail "$s" $? $R/bench.log
+      timeout -k 10 400 python -u bench.py --full > $R/bench.log 2>&1 || fail "$s" $? $R/bench.log
       tail -1 $R/bench.log > $R/bench_line.json; cut -c1-300 $R/bench_line.json ;;
     config1)
-      timeout -k 10 300 python -u bench.py --mazes 4096 --horizon 32 --no-cpu-baseline > $R/bench_config1.log 2>&1 \
+      timeout -k 10 300 python -u bench.py --full --mazes 4096 --horizon 32 --no-cpu-baseline > $R/bench_config1.log 2>&1 \
         || fail "$s" $? $R/bench_config1.log
       tail -1 $R/bench_config1.log > $R/bench_line_config1_4096.json; cut -c1-300 $R/bench_line_config1_4096.json ;;
     config3)
@@ -82,7 +82,7 @@ for s in "$@"; do
       cat $R/bench_wgrad_dma.jsonl ;;
     dp)
       MARLMAZE_DP_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --mazes 8192 --steps 2 --warmup 1 \
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --mazes 8192 --steps 2 --warmup 1 --full \
         > $R/dp_rehearsal.log 2>&1 || fail "$s" $? $R/dp_rehearsal.log
       tail -1 $R/dp_rehearsal.log | cut -c1-300 ;;
     *) echo "unknown step $s"; exit 2 ;;
