@@ -498,6 +498,53 @@ int mm_head_sample_ex(const float* h, int ldh, int K, const float* w, const floa
  * 0, K <= 1024, 16-byte aligned rows); M * ldh * 4 < 2^31. */
 int mm_heads_fwd(const float* h, int ldh, int K, const float* w, const float* b, int M, float* logits, void* stream);
 
+/* Action selection with a mode (csrc/eval_kernels.hip).
+ *   MM_ACT_SAMPLE  the draws of mm_sample / mm_head_sample_ex: the same actions, log-probs and logits bit
+ *                  for bit at the same (seed, offset, offset_dev, row);
+ *   MM_ACT_GREEDY  the most likely action, no draws (seed, offset and offset_dev are ignored): the move is
+ *                  the LOWEST index among the legal moves whose logit is the maximum (torch.argmax), the
+ *                  mark is masks[:,5] && mark_logit > 0 (sigmoid > 0.5: a logit of exactly 0 does not
+ *                  mark); logp is log pi of that action by the sampler's formula.  No legal move: move 4 and
+ *                  a NaN log-prob, as the sampler.
+ * mm_head_act: mm_head_sample_ex's operands, rules (K % 4 == 0, K <= 1024, 16-byte aligned rows) and per-row
+ * arithmetic: its logits equal mm_heads_fwd's and mm_head_sample_ex's bit for bit.
+ * mm_act: mm_sample's operands (logits given). */
+#define MM_ACT_SAMPLE 0
+#define MM_ACT_GREEDY 1
+int mm_head_act(const float* h, int ldh, int K, const float* w, const float* b, const uint8_t* masks, int M, int mode,
+                uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int8_t* actions, float* logp,
+                float* joint_logp, float* logits, void* stream);
+int mm_act(const float* move_logits, const float* mark_logits, const uint8_t* masks, int M, int mode, uint64_t seed,
+           uint64_t offset, int8_t* actions, float* logp, float* joint_logp, void* stream);
+
+/* Episode totals of an evaluation run (csrc/eval_kernels.hip): totals [MM_EVAL_WORDS] uint64 and counted [n]
+ * int32 on the device.  Every word is an integer, so the totals are exact and do not depend on the order
+ * in which the workgroups add to them.
+ * mm_eval_init: counted = 0, totals = 0, the min word = UINT64_MAX.
+ * mm_eval_accum (after every env step, on its done [n] u8, reward [n] f32 and ep_stats [n,2] int32 =
+ * (length, shortest_path_len), 8-byte aligned): every maze m with done[m] != 0 and counted[m] < quota has
+ * counted[m] incremented and its episode added: solved when reward[m] == 1.0f, timed out otherwise.
+ * Episodes past the quota are ignored: every maze contributes its first `quota` episodes, however fast it
+ * finishes them.  len >= 0 is expected. */
+#define MM_EVAL_WORDS 32
+#define MM_EV_EPISODES 0          /* counted episodes */
+#define MM_EV_SOLVED 1            /* solved episodes */
+#define MM_EV_TIMEOUTS 2          /* timed-out episodes */
+#define MM_EV_SUM_LEN 3           /* sum of len over all counted episodes */
+#define MM_EV_SUM_LEN_SOLVED 4    /* sum of len over solved episodes */
+#define MM_EV_SUM_SHORT_SOLVED 5  /* sum of shortest over solved episodes */
+#define MM_EV_MIN_LEN_SOLVED 6    /* min of len over solved episodes (UINT64_MAX: none) */
+#define MM_EV_MAX_LEN_SOLVED 7    /* max of len over solved episodes */
+#define MM_EV_SUM_RATIO_Q16 8     /* sum of floor(len * 65536 / shortest) over solved episodes, shortest > 0 */
+#define MM_EV_BAD_SHORT 9         /* solved episodes with shortest <= 0 (not in the ratio sum or the histogram) */
+/* (words 10..15: zero) */
+#define MM_EV_HIST0 16            /* words 16..31: histogram over solved episodes with shortest > 0, bin */
+#define MM_EV_HIST_BINS 16        /* clamp(4 * len / shortest - 4, 0, 15) (integer division): quarter steps of
+                                   * len / shortest from 1.0, the last bin open */
+int mm_eval_init(uint64_t* totals, int32_t* counted, int n, void* stream);
+int mm_eval_accum(const uint8_t* done, const float* reward, const int32_t* ep_stats, int n, int quota,
+                  int32_t* counted, uint64_t* totals, void* stream);
+
 /* The critic's value in one launch (networks.py:87-102, inference: PPO.get_batch's per-step
  * self.critic(obs), PPO.py:111): v [M] = w2 . ReLU(w1 ReLU(w0 x + b0) + b1) + b2 for x [M, K0] (row
  * stride ldx), w0 [H0, K0], w1 [H1, H0], w2 [1, H1] (nn.Linear layouts), on the fp32 MFMA (exact fmaf

@@ -78,5 +78,46 @@ __device__ __forceinline__ float sample_row(const float ml[5], float kl, const u
     return lp;
 }
 
+// The deterministic sibling of sample_row (no draws): the same masked-logit arithmetic, the most likely action.
+// Move: the lowest index among the legal moves whose logit is the maximum (torch.argmax's first occurrence).
+// Mark: allowed and mark_logit > 0 (sigmoid > 0.5; a logit of exactly 0 does not mark).  Returns log pi(a|s) of
+// that action by sample_row's formula; no legal move: move 4 and NaN, as there.
+__device__ __forceinline__ float greedy_row(const float ml[5], float kl, const uint8_t* __restrict__ mk, int& move,
+                                            int& mark) {
+    float l[5];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        l[j] = mk[j] ? ml[j] : -INFINITY;  // masked_fill(~mask, -inf)
+        mx = fmaxf(mx, l[j]);
+    }
+    float sum = 0.f;
+    int mv = -1, first = -1;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        sum += mk[j] ? expf(l[j] - mx) : 0.f;
+        if (!mk[j]) continue;
+        if (first < 0) first = j;
+        if (mv < 0 && l[j] == mx) mv = j;
+    }
+    if (mv < 0) mv = first;  // (legal logits all NaN: fmaxf skipped them; the log-prob is NaN either way)
+    float lp;
+    if (mv < 0) {  // no legal move
+        mv = 4;
+        lp = NAN;
+    } else {
+        lp = (l[mv] - mx) - logf(sum);
+    }
+    int mk5 = 0;
+    float pm = 0.f;
+    if (mk[5]) {
+        pm = 1.f / (1.f + expf(-kl));
+        mk5 = kl > 0.f ? 1 : 0;
+    }
+    lp += logf(mk5 ? pm : 1.f - pm);
+    move = mv;
+    mark = mk5;
+    return lp;
+}
 
 }  // namespace mm

@@ -759,7 +759,145 @@ class PPO:
             self.range_redos += 1
         return hist
 
-    def train(self):
+    # ------------------------------------------------------------------
+    # evaluation
+    # ------------------------------------------------------------------
+    @torch.no_grad()
+    def evaluate(self, episodes_per_env=1, greedy=True, n_envs=None, env_config=None, seed_base=0, eval_seed=0,
+                 poll=16, record=False):
+        """How good is the policy: ``episodes_per_env`` whole episodes on each of ``n_envs`` fresh mazes
+        (seeds ``seed_base + rank n + i``; configuration ``env_config``, else this agent's), every agent
+        taking its most likely action (``greedy``) or drawing one (Philox key ``eval_seed``, counter = the
+        step).  Per step: front-end, trunk, mm_head_act, the env step with auto-reset, mm_eval_accum; the
+        totals are read every ``poll`` steps and the run ends when every maze has contributed its episodes
+        (each maze its first ``episodes_per_env``, see marlmaze.evaluate) -- at the latest after
+        ``episodes_per_env * max_timestep`` steps, where an episode is cut off.  Under DP the totals are those
+        of all ranks' mazes.
+
+        Returns marlmaze.evaluate.result_from_words' dict plus ``env_steps`` and ``seconds``; with ``record``
+        also a dict of the per-step ``actions`` [T, n, 2, 2], ``done`` [T, n] and ``reward`` [T, n] of this
+        rank (for small n).  Training does not notice the call: it uses an environment and buffers of its own
+        and leaves the rollout's environment, buffers, sampler offset, the range-guard state and every random
+        generator as they are."""
+        import time
+
+        from . import _lib
+        from .evaluate import NONE_MIN, result_from_words
+
+        n, E = int(n_envs if n_envs is not None else self.n_envs), int(episodes_per_env)
+        if n < 1 or E < 1:
+            raise ValueError("evaluate needs n_envs >= 1 and episodes_per_env >= 1")
+        kw = dict(env_config) if env_config is not None else self._env_kwargs()
+        kw.pop("seed_base", None)
+        dev, dp = self.device, self.dp
+        seeds = np.arange(n, dtype=np.uint64) + np.uint64(int(seed_base) + dp.rank * n)
+        args = (n, E, seeds, kw, "greedy" if greedy else "sample", int(eval_seed) + 7919 * dp.rank,
+                max(1, int(poll)), bool(record))
+
+        # The fp16-plane GEMMs (x2, f16) raise the library's range flag, which belongs to the rollout and the
+        # update (_range_guarded).  It is only looked at here, never cleared while it carries their state: raised
+        # already -> this run uses x3 (which leaves it alone); raised BY this run -> back to clear, its state
+        # before, and the run is repeated at x3, as the update does.  Under DP both decisions are taken from the
+        # MAX over ranks (_range_flags' rule): every rank runs at the same precision and issues the same
+        # collectives
+        def flag_anywhere():
+            mine = x3.range_flag(clear=False)
+            return bool(int(mine)), bool(int(dp.allreduce_max(mine.clone())))
+
+        guarded = self.flat is not None and self.actor.gemm_prec != "x3"
+        prec = self.actor.gemm_prec
+        try:
+            if guarded and flag_anywhere()[1]:
+                self.actor.gemm_prec = "x3"
+                guarded = False
+            T, words, rec, t0 = self._eval_run(*args)
+            if guarded:
+                mine, anywhere = flag_anywhere()
+                if anywhere:
+                    if mine:  # raised by this run (it was clear before): clear again
+                        x3.range_flag(clear=True)
+                    warnings.warn(f"marlmaze: a {prec} GEMM operand of the evaluation reached |x| >= 2^15 (fp16 "
+                                  "planes): the evaluation is repeated at x3")
+                    self.actor.gemm_prec = "x3"
+                    T, words, rec, t0 = self._eval_run(*args)
+            seconds = time.perf_counter() - t0
+        finally:
+            self.actor.gemm_prec = prec
+        if dp.active:  # sums, and max / min (as the max of a complement) of the two extreme words
+            mn, mx = words[_lib.EV_MIN_LEN_SOLVED], words[_lib.EV_MAX_LEN_SOLVED]
+            w = torch.tensor([0 if k == _lib.EV_MIN_LEN_SOLVED else v for k, v in enumerate(words)],
+                             dtype=torch.int64, device=dev)
+            ext = torch.tensor([mx, 2**62 - mn if mn != NONE_MIN else 0], dtype=torch.int64, device=dev)
+            words = dp.allreduce_sum(w).tolist()
+            ext = dp.allreduce_max(ext).tolist()
+            words[_lib.EV_MAX_LEN_SOLVED] = ext[0]
+            words[_lib.EV_MIN_LEN_SOLVED] = 2**62 - ext[1] if ext[1] > 0 else NONE_MIN
+        res = result_from_words(words)
+        res["env_steps"] = n * T * dp.world
+        res["seconds"] = seconds
+        return (res, rec) if record else res
+
+    def _eval_run(self, n, E, seeds, kw, mode, key, poll, record):
+        """One evaluation at the actor's current GEMM precision on a fresh VecMaze: (steps, this rank's 32 words,
+        the recorded steps or None, the stepping loop's start time).  The side-stream maze pre-generation is
+        queued once per poll window, as the rollout queues it once per horizon (VecMaze.defer_pregen)."""
+        import time
+
+        from . import _lib
+        from .evaluate import EvalTotals
+
+        dev, dp = self.device, self.dp
+        venv = VecMaze(n, seeds=seeds, device=dev, **kw)
+        max_steps = E * venv.max_timestep  # k_step ends an episode at t >= max_timestep
+        obs = torch.empty((n, 2, 65), dtype=torch.float32, device=dev)
+        masks = torch.empty((n, 2, 6), dtype=torch.uint8, device=dev)
+        act = torch.empty((n, 2, 2), dtype=torch.int8, device=dev)
+        rowlp = torch.empty(2 * n, dtype=torch.float32, device=dev)
+        rew = torch.empty(n, dtype=torch.float32, device=dev)
+        done = torch.empty(n, dtype=torch.uint8, device=dev)
+        stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        tot = EvalTotals(n, E, device=dev)
+        head_w, head_b = self.actor.heads()
+        rec = dict(actions=[], done=[], reward=[]) if record else None
+        venv.reset(obs=obs, masks=masks)
+        torch.cuda.synchronize(dev)  # the caller's `seconds` is the stepping loop's: the mazes exist
+        t0, t = time.perf_counter(), 0
+        venv.defer_pregen = True
+        try:
+            with x3.cached_packs():  # the weights are fixed: packed once
+                while True:
+                    self.actor.act(obs.view(2 * n, 65), head_w, head_b, masks.view(2 * n, 6), mode, key, t,
+                                   actions=act.view(2 * n, 2), logp=rowlp)
+                    venv.step(act, auto_reset=True, obs=obs, masks=masks, reward=rew, done=done, ep_stats=stats)
+                    tot.accum(done, rew, stats)
+                    t += 1
+                    if rec is not None:
+                        rec["actions"].append(act.clone())
+                        rec["done"].append(done.clone())
+                        rec["reward"].append(rew.clone())
+                    if t % poll and t < max_steps:
+                        continue
+                    venv.defer_pregen = False  # the window's finished mazes get their next mazes generated
+                    venv.flush_pregen()
+                    venv.defer_pregen = True
+                    words = tot.words()  # the host synchronisation
+                    count = torch.tensor([words[_lib.EV_EPISODES]], dtype=torch.int64, device=dev)
+                    if int(dp.allreduce_sum(count)) == n * E * dp.world:  # every rank stops at the same step
+                        break
+                    if t >= max_steps:
+                        raise RuntimeError(f"evaluate: {int(count)} of {n * E * dp.world} episodes after {t} "
+                                           f"steps (max_timestep {venv.max_timestep})")
+        finally:
+            venv.defer_pregen = False
+            venv.flush_pregen()
+            venv._quiesce_pregen()  # the side stream's generation ends before the buffers go
+        if rec is not None:
+            rec = {k: torch.stack(v) for k, v in rec.items()}
+        return t, words, rec, t0
+
+    def train(self, eval_every=0, eval_kwargs=None):
+        """PPO.train (PPO.py:22-44).  ``eval_every`` > 0: after every ``eval_every``-th epoch, evaluate(**eval_kwargs)
+        is stored in that epoch's history entry under "eval" (and printed as one line)."""
         for epoch in range(self.epochs):
             b_obs, b_act, b_lp, b_sp, ep_lens, b_masks, b_advs, b_vals = self.get_batch()
             hist = self.update(b_obs, b_act, b_lp, b_masks, b_advs, b_vals)
@@ -775,6 +913,12 @@ class PPO:
                 print(f"Mazes solved in current epoch: {stats['episodes']}")
                 print(f"Average Exit Time: {stats['mean_len']}")
                 print(f"Average Length of Shortest Path: {stats['mean_shortest']}", flush=True)
+            if eval_every > 0 and (epoch + 1) % eval_every == 0:
+                from .evaluate import format_result
+
+                stats["eval"] = self.evaluate(**(eval_kwargs or {}))
+                if self.verbose:
+                    print(format_result(stats["eval"]), flush=True)
             if self.save and self.dp.rank == 0:
                 self.save_parameters()
 
@@ -782,12 +926,17 @@ class PPO:
     # single-sample API of the reference
     # ------------------------------------------------------------------
     @torch.no_grad()
-    def get_action(self, obs, action_mask):
-        """PPO.get_action (PPO.py:170-186): ([move, mark], log_prob (1,1))."""
+    def get_action(self, obs, action_mask, greedy=False):
+        """PPO.get_action (PPO.py:170-186): ([move, mark], log_prob (1,1)).  ``greedy``: the most likely action
+        (ops.act: the lowest-index legal move with the maximal logit, a mark where its logit is > 0) and its
+        log-prob; no draw, the sampler's offset stays where it is."""
         ml, kl = self.actor(obs)
         mk = torch.as_tensor(np.asarray(action_mask, dtype=np.uint8), device=self.device).view(1, 6)
-        a, lp, _ = ops.sample(ml, kl.reshape(-1), mk, self.sample_seed, self._sample_offset)
-        self._sample_offset += 1
+        if greedy:
+            a, lp, _ = ops.act(ml, kl.reshape(-1), mk, mode="greedy")
+        else:
+            a, lp, _ = ops.sample(ml, kl.reshape(-1), mk, self.sample_seed, self._sample_offset)
+            self._sample_offset += 1
         a = a.cpu().tolist()[0]
         return [a[0], a[1]], lp.view(1, 1)
 

@@ -24,6 +24,14 @@ ST_BAD_MOVE = 2
 
 GAE_AUTO, GAE_COLUMN, GAE_WALK, GAE_SCAN = 0, 1, 2, 3  # mm_gae_ex algorithms
 
+ACT_SAMPLE, ACT_GREEDY = 0, 1  # MM_ACT_* (mm_head_act, mm_act)
+ACT_MODES = {"sample": ACT_SAMPLE, "greedy": ACT_GREEDY}
+
+EVAL_WORDS = 32  # MM_EVAL_WORDS: uint64 words of an evaluation's totals (mm_eval_init, mm_eval_accum)
+EV_EPISODES, EV_SOLVED, EV_TIMEOUTS, EV_SUM_LEN, EV_SUM_LEN_SOLVED, EV_SUM_SHORT_SOLVED = 0, 1, 2, 3, 4, 5  # MM_EV_*
+EV_MIN_LEN_SOLVED, EV_MAX_LEN_SOLVED, EV_SUM_RATIO_Q16, EV_BAD_SHORT = 6, 7, 8, 9
+EV_HIST0, EV_HIST_BINS = 16, 16
+
 AF_KNOWS_END = 1
 AF_SEES_END = 2
 AF_OTHER_KNOWS = 4
@@ -47,8 +55,8 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_gemm_range_flag", "mm_gemm_nt_h", "mm_gemm_a16_ok", "mm_gemm_wgrad_h", "mm_gemm_wgrad_partials_h",
            "mm_heads_fwd_h16", "mm_x3_heads_bwd_h16", "mm_trunk3_ok", "mm_trunk3",
            "mm_trunk3_head_sample_ok", "mm_trunk3_head_sample", "mm_actor_front_fwd_h16",
-           "mm_actor_front_fwd_h16_ex")
-VERSION = 307  # mm_version() this binding is written for
+           "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum")
+VERSION = 308  # mm_version() this binding is written for
 
 PREC_X3, PREC_F16, PREC_X2 = 0, 1, 2  # MM_PREC_*
 FRONT_BWD = {"mfma": 0, "valu": 1}  # MM_FRONT_BWD_*
@@ -151,6 +159,14 @@ def lib():
         L.mm_critic_value.restype = i32
         L.mm_head_sample_ex.argtypes = [P, i32, i32, P, P, P, i32, u64, u64, P, P, P, P, P, P]
         L.mm_head_sample_ex.restype = i32
+        L.mm_head_act.argtypes = [P, i32, i32, P, P, P, i32, i32, u64, u64, P, P, P, P, P, P]
+        L.mm_head_act.restype = i32
+        L.mm_act.argtypes = [P, P, P, i32, i32, u64, u64, P, P, P, P]
+        L.mm_act.restype = i32
+        L.mm_eval_init.argtypes = [P, P, i32, P]
+        L.mm_eval_init.restype = i32
+        L.mm_eval_accum.argtypes = [P, P, P, i32, i32, P, P, P]
+        L.mm_eval_accum.restype = i32
         L.mm_x3_tp_len.argtypes = [i32, i32]
         L.mm_x3_tp_len.restype = ctypes.c_long
         L.mm_x3_tp_pack.argtypes = [P, i32, i32, i32, i32, P, P]

@@ -144,9 +144,9 @@ class Maze:
         for row in self.layout:
             print(row)
 
-    def display_policy(self, id=-1, steps=200, path=None):
+    def display_policy(self, id=-1, steps=200, path=None, greedy=False):
         """maze.py:466-522 without the window: `steps` policy steps from a reset, one frame per state
-        (returned; an animated GIF at `path` when given)."""
+        (returned; an animated GIF at `path` when given).  ``greedy``: the most likely actions, no draws."""
         from . import viewer
 
-        return viewer.display_policy(self, id=id, steps=steps, path=path)
+        return viewer.display_policy(self, id=id, steps=steps, path=path, greedy=greedy)

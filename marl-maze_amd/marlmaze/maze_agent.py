@@ -32,11 +32,11 @@ class Agent:
         self.tag = tag
 
     # ------------------------------------------------------------------
-    def get_action(self, obs, mask):
-        """maze_agent.py:81-83."""
+    def get_action(self, obs, mask, greedy=False):
+        """maze_agent.py:81-83; ``greedy``: the brain's most likely action instead of a draw."""
         from math import exp
 
-        action, prob = self.brain.get_action(obs, mask)
+        action, prob = self.brain.get_action(obs, mask, greedy=True) if greedy else self.brain.get_action(obs, mask)
         return action, exp(float(prob))
 
     def get_observations(self):

@@ -619,6 +619,15 @@ class Actor(nn.Module):
         return ops.head_sample(self._mlp(h0), head_w, head_b, masks, seed, offset, actions=actions, logp=logp,
                                joint_logp=joint_logp, offset_dev=offset_dev)
 
+    def act(self, x, head_w, head_b, masks, mode="greedy", seed=0, offset=0, actions=None, logp=None,
+            joint_logp=None):
+        """Evaluation's actor step: front-end, trunk (_mlp) and ops.head_act -- ``mode`` "greedy" (the most
+        likely action, no draws) or "sample" (sample_actions' draws at the same seed and offset)."""
+        from . import ops
+
+        return ops.head_act(self._mlp(self._front(x)), head_w, head_b, masks, mode=mode, seed=seed, offset=offset,
+                            actions=actions, logp=logp, joint_logp=joint_logp)
+
     def _front(self, x):
         """Projection + attention (networks.py:31-34)."""
         x = torch.as_tensor(x, dtype=torch.float32, device=self.move_head.weight.device).reshape(-1, OBS_SPACE)

@@ -92,3 +92,55 @@ def head_sample(h, head_w, head_b, masks, seed, offset, actions=None, logp=None,
                                             _lib.ptr(joint_logp), _lib.ptr(logits), _lib.stream_ptr()),
                "mm_head_sample_ex")
     return actions, logp, joint_logp
+
+
+def _act_mode(mode):
+    if mode not in _lib.ACT_MODES:
+        raise ValueError(f"mode must be 'greedy' or 'sample', not {mode!r}")
+    return _lib.ACT_MODES[mode]
+
+
+def act(move_logits, mark_logits, masks, mode="greedy", seed=0, offset=0, actions=None, logp=None, joint_logp=None):
+    """``sample`` with a mode (mm_act): "sample" draws exactly as ``sample`` does, "greedy" takes the most
+    likely action -- the lowest-index legal move with the maximal logit, a mark where it is allowed and
+    the mark logit is > 0 -- and ignores seed and offset.  Returns actions, logp, joint_logp."""
+    M = move_logits.shape[0]
+    dev = move_logits.device
+    ml = move_logits.contiguous()
+    kl = mark_logits.contiguous()
+    mk = masks.to(torch.uint8).contiguous()
+    if actions is None:
+        actions = torch.empty((M, 2), dtype=torch.int8, device=dev)
+    if logp is None:
+        logp = torch.empty(M, dtype=torch.float32, device=dev)
+    if joint_logp is None:
+        joint_logp = torch.empty((M + 1) // 2, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mm_act(_lib.ptr(ml), _lib.ptr(kl), _lib.ptr(mk), int(M), _act_mode(mode),
+                                 int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _lib.ptr(actions),
+                                 _lib.ptr(logp), _lib.ptr(joint_logp), _lib.stream_ptr()), "mm_act")
+    return actions, logp, joint_logp
+
+
+def head_act(h, head_w, head_b, masks, mode="greedy", seed=0, offset=0, actions=None, logp=None, joint_logp=None,
+             logits=None, offset_dev=None):
+    """``head_sample`` with a mode (csrc/eval_kernels.hip k_head_act): the same logits bit for bit; "sample"
+    reproduces ``head_sample``, "greedy" takes the most likely action (see ``act``).  Returns actions,
+    logp, joint_logp."""
+    M, K = h.shape
+    dev = h.device
+    hc = h.contiguous()
+    w = head_w.contiguous()
+    b = head_b.contiguous()
+    mk = masks.to(torch.uint8).contiguous()
+    if actions is None:
+        actions = torch.empty((M, 2), dtype=torch.int8, device=dev)
+    if logp is None:
+        logp = torch.empty(M, dtype=torch.float32, device=dev)
+    if joint_logp is None:
+        joint_logp = torch.empty((M + 1) // 2, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mm_head_act(_lib.ptr(hc), int(hc.stride(0)), int(K), _lib.ptr(w), _lib.ptr(b),
+                                      _lib.ptr(mk), int(M), _act_mode(mode), int(seed) & (2**64 - 1),
+                                      int(offset) & (2**64 - 1), _lib.ptr(offset_dev), _lib.ptr(actions),
+                                      _lib.ptr(logp), _lib.ptr(joint_logp), _lib.ptr(logits), _lib.stream_ptr()),
+               "mm_head_act")
+    return actions, logp, joint_logp

@@ -193,13 +193,15 @@ def draw_hidden_maze(maze, agent_tag):
     return cv.img
 
 
-def display_policy(maze, id=-1, steps=200, path=None):
+def display_policy(maze, id=-1, steps=200, path=None, greedy=False):
     """maze.py:466-522 without the window: reset, then `steps` policy steps (a reset after done),
-    one frame per state.  Returns the frames; with `path`, also writes them as an animated GIF."""
+    one frame per state.  Returns the frames; with `path`, also writes them as an animated GIF.
+    ``greedy``: every agent takes its most likely action instead of drawing one."""
     obs, masks = maze.reset()
     frames = [draw_maze(maze, id)]
     for _ in range(int(steps)):
-        action = [list(a.get_action(obs[i], masks[i])[0]) for i, a in enumerate(maze.agents)]
+        kw = {"greedy": True} if greedy else {}
+        action = [list(a.get_action(obs[i], masks[i], **kw)[0]) for i, a in enumerate(maze.agents)]
         obs, masks, _, done = maze.step(action)
         frames.append(draw_maze(maze, id))
         if done:
