@@ -498,7 +498,8 @@ int mm_head_sample_ex(const float* h, int ldh, int K, const float* w, const floa
  * 0, K <= 1024, 16-byte aligned rows); M * ldh * 4 < 2^31. */
 int mm_heads_fwd(const float* h, int ldh, int K, const float* w, const float* b, int M, float* logits, void* stream);
 
-/* Action selection with a mode (csrc/eval_kernels.hip).
+/* Action selection with a mode (csrc/rl_kernels.hip: the sampler's kernels; mm_sample and mm_head_sample_ex
+ * are the MM_ACT_SAMPLE form of these two).
  *   MM_ACT_SAMPLE  the draws of mm_sample / mm_head_sample_ex: the same actions, log-probs and logits bit
  *                  for bit at the same (seed, offset, offset_dev, row);
  *   MM_ACT_GREEDY  the most likely action, no draws (seed, offset and offset_dev are ignored): the move is

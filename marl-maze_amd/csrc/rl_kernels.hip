@@ -14,11 +14,14 @@
 //   k_gae_scan  the same recursion as an affine-map suffix scan (wavefront
 //             shuffles + LDS): parallel inside episodes, reassociated (fp32
 //             rounding differs; within 1e-5 relative).
-//   k_sample  PPO.get_action (PPO.py:170-186) for every agent row: masked
-//             categorical move + Bernoulli mark, per-agent and joint log-prob,
-//             counter-based Philox4x32-10 draws.
-//   k_head_sample  the actor's two heads (networks.py:38-41) fused with
-//             k_sample's draw: last hidden layer -> actions, log-probs.
+//   k_act     PPO.get_action (PPO.py:170-186) for every agent row, with a
+//             mode: MM_ACT_SAMPLE draws (masked categorical move + Bernoulli
+//             mark, counter-based Philox4x32-10), MM_ACT_GREEDY takes the most
+//             likely action; per-agent and joint log-prob.
+//   k_head_act  the actor's two heads (networks.py:38-41) fused with k_act's
+//             choice: last hidden layer -> actions, log-probs (the rollout's
+//             unfused actor step, and evaluation's).
+//   k_heads_fwd  the heads alone (the update's forward), the same row code.
 //   k_ppo_loss / k_ppo_loss_bwd  the update's policy side (PPO.py:62-72 with
 //             get_log_probs PPO.py:154-168): per-agent masked log-softmax of
 //             the move logits + masked Bernoulli mark log-prob, joint log-prob,
@@ -199,13 +202,14 @@ __global__ __launch_bounds__(256) void k_gae_scan(GaeArgs a) {
         });
 }
 
-// Philox4x32-10 and sample_row (one agent row of PPO.get_action): policy_device.h, shared with the fused
-// trunk + heads + sampler of x3mlp.hip.
+// Philox4x32-10, act_row (one agent row of PPO.get_action) and the heads' row GEMV: policy_device.h, shared with
+// the fused trunk + heads + sampler of x3mlp.hip.
 
 // One thread per maze: rows 2i (agent 0) and 2i+1 (agent 1).
-__global__ void k_sample(const float* __restrict__ ml, const float* __restrict__ kl, const uint8_t* __restrict__ masks,
-                         int M, uint64_t seed, uint64_t offset, int8_t* __restrict__ act, float* __restrict__ logp,
-                         float* __restrict__ joint) {
+template <int MODE>
+__global__ void k_act(const float* __restrict__ ml, const float* __restrict__ kl, const uint8_t* __restrict__ masks,
+                      int M, uint64_t seed, uint64_t offset, int8_t* __restrict__ act, float* __restrict__ logp,
+                      float* __restrict__ joint) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int nm = (M + 1) / 2;
     if (i >= nm) return;
@@ -218,7 +222,7 @@ __global__ void k_sample(const float* __restrict__ ml, const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 5; j++) l[j] = ml[(size_t)row * 5 + j];
         int move, mark;
-        const float lp = sample_row(l, kl[row], masks + (size_t)row * MM_MASK_DIM, row, seed, offset, move, mark);
+        const float lp = act_row<MODE>(l, kl[row], masks + (size_t)row * MM_MASK_DIM, row, seed, offset, move, mark);
         act[2 * row] = (int8_t)move;
         act[2 * row + 1] = (int8_t)mark;
         if (logp) logp[row] = lp;
@@ -228,26 +232,26 @@ __global__ void k_sample(const float* __restrict__ ml, const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------
-// fused policy head + sampler
+// fused policy head + action
 // ---------------------------------------------------------------------------
 // logits = h W^T + b for the concatenated heads W = [move_head; mark_head]
-// [6, K] (networks.py:38-41), then sample_row -- the logits never leave the
-// registers.  8 lanes per row (each lane a 4-column stride of the row, so a
-// row's 8 lanes read 128 contiguous bytes per step), 32 rows = 16 mazes per
-// 256-thread workgroup; head weights staged in LDS.
-constexpr int kHsLanes = 8;
+// [6, K] (networks.py:38-41), then act_row -- the logits never leave the
+// registers.  The row layout of policy_device.h (8 lanes per row), 32 rows =
+// 16 mazes per 256-thread workgroup; head weights staged in LDS.
+constexpr int kHsLanes = kHeadLanes;
 constexpr int kHsRows = 32;
 constexpr int kHsMaxK = 1024;
 
-__global__ __launch_bounds__(kHsLanes* kHsRows) void k_head_sample(const float* __restrict__ h, int ldh, int K,
-                                                                   const float* __restrict__ w,
-                                                                   const float* __restrict__ b,
-                                                                   const uint8_t* __restrict__ masks, int M,
-                                                                   uint64_t seed, uint64_t offset,
-                                                                   const uint64_t* __restrict__ offset_dev,
-                                                                   int8_t* __restrict__ act, float* __restrict__ logp,
-                                                                   float* __restrict__ joint,
-                                                                   float* __restrict__ logits) {
+template <int MODE>
+__global__ __launch_bounds__(kHsLanes* kHsRows) void k_head_act(const float* __restrict__ h, int ldh, int K,
+                                                                const float* __restrict__ w,
+                                                                const float* __restrict__ b,
+                                                                const uint8_t* __restrict__ masks, int M,
+                                                                uint64_t seed, uint64_t offset,
+                                                                const uint64_t* __restrict__ offset_dev,
+                                                                int8_t* __restrict__ act, float* __restrict__ logp,
+                                                                float* __restrict__ joint,
+                                                                float* __restrict__ logits) {
     __shared__ __attribute__((aligned(16))) float W[6 * kHsMaxK];
     // loads batched ahead of the LDS writes: one L2 round trip, not one per element
     constexpr int kB = 8;
@@ -269,49 +273,12 @@ __global__ __launch_bounds__(kHsLanes* kHsRows) void k_head_sample(const float* 
     const int row = blockIdx.x * kHsRows + threadIdx.x / kHsLanes;
     const bool valid = row < M;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (valid) {
-        const float* hr = h + (size_t)row * ldh;
-        for (int c = 4 * j; c < K; c += 4 * kHsLanes) {
-            const float4 hv = *reinterpret_cast<const float4*>(hr + c);
-#pragma unroll
-            for (int o = 0; o < 6; o++) {
-                const float4 wv = *reinterpret_cast<const float4*>(W + o * K + c);
-                acc[o] = fmaf(hv.x, wv.x, acc[o]);
-                acc[o] = fmaf(hv.y, wv.y, acc[o]);
-                acc[o] = fmaf(hv.z, wv.z, acc[o]);
-                acc[o] = fmaf(hv.w, wv.w, acc[o]);
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < 6; o++) {  // butterfly over the row's 8 lanes: every lane holds the sums
-#pragma unroll
-        for (int d = kHsLanes / 2; d > 0; d >>= 1) acc[o] += __shfl_xor(acc[o], d);
-    }
-    float lp = 0.f;
-    if (valid && j == 0) {
-        float l[5];
-#pragma unroll
-        for (int o = 0; o < 5; o++) l[o] = acc[o] + b[o];
-        const float kl = acc[5] + b[5];
-        int move, mark;
-        const uint64_t off = offset + (offset_dev ? *offset_dev : 0ull);  // a device base: graph replays advance it
-        lp = sample_row(l, kl, masks + (size_t)row * MM_MASK_DIM, row, seed, off, move, mark);
-        act[2 * row] = (int8_t)move;
-        act[2 * row + 1] = (int8_t)mark;
-        if (logp) logp[row] = lp;
-        if (logits) {
-#pragma unroll
-            for (int o = 0; o < 5; o++) logits[(size_t)row * 6 + o] = l[o];
-            logits[(size_t)row * 6 + 5] = kl;
-        }
-    }
-    // joint log-prob of maze row/2: rows 2i and 2i+1 are adjacent 8-lane groups
-    const float other = __shfl_down(lp, kHsLanes);
-    if (joint && valid && j == 0 && (row & 1) == 0) joint[row >> 1] = lp + (row + 1 < M ? other : 0.f);
+    if (valid) heads_row_dot(h + (size_t)row * ldh, K, W, K, j, acc);
+    heads_butterfly(acc);
+    heads_finish<MODE>(acc, b, masks, row, M, valid && j == 0, seed, offset, offset_dev, act, logp, joint, logits);
 }
 
-// The heads alone (the update's forward, networks.py:38-41): logits [M, 6] = h W^T + b with k_head_sample's
+// The heads alone (the update's forward, networks.py:38-41): logits [M, 6] = h W^T + b with k_head_act's
 // arithmetic per row -- the same lanes, per-lane fma order and butterfly -- so the update's logits equal the
 // rollout's bit for bit at the same parameters (the PPO ratio is exactly 1 before the first step).  A
 // streaming GEMV (443 MB of h per 419,430-row minibatch): NS (= ceil(K / 32)) 16-byte loads per lane all in
@@ -368,36 +335,11 @@ __global__ __launch_bounds__(kHsLanes* kHsRows) void k_heads_fwd(const float* __
             }
         }
 #pragma unroll
-        for (int s = 0; s < NS; s++) {
-            const int c = 4 * j + 32 * s;
-#pragma unroll
-            for (int o = 0; o < 6; o++) {
-                const float4 wv = *reinterpret_cast<const float4*>(W + o * kSpan + c);
-                acc[o] = fmaf(hv[s].x, wv.x, acc[o]);
-                acc[o] = fmaf(hv[s].y, wv.y, acc[o]);
-                acc[o] = fmaf(hv[s].z, wv.z, acc[o]);
-                acc[o] = fmaf(hv[s].w, wv.w, acc[o]);
-            }
-        }
+        for (int s = 0; s < NS; s++) heads_fma4(hv[s], W + 4 * j + 32 * s, kSpan, acc);
     } else if (row < M) {
-        const float* hr = h + (size_t)row * ldh;
-        for (int c = 4 * j; c < K; c += 4 * kHsLanes) {
-            const float4 hv = *reinterpret_cast<const float4*>(hr + c);
-#pragma unroll
-            for (int o = 0; o < 6; o++) {
-                const float4 wv = *reinterpret_cast<const float4*>(W + o * kSpan + c);
-                acc[o] = fmaf(hv.x, wv.x, acc[o]);
-                acc[o] = fmaf(hv.y, wv.y, acc[o]);
-                acc[o] = fmaf(hv.z, wv.z, acc[o]);
-                acc[o] = fmaf(hv.w, wv.w, acc[o]);
-            }
-        }
+        heads_row_dot(h + (size_t)row * ldh, K, W, kSpan, j, acc);
     }
-#pragma unroll
-    for (int o = 0; o < 6; o++) {
-#pragma unroll
-        for (int d = kHsLanes / 2; d > 0; d >>= 1) acc[o] += __shfl_xor(acc[o], d);
-    }
+    heads_butterfly(acc);
     // lane j < 6 of the row writes logit j: a row's 24 bytes, the workgroup's 32 rows contiguous
     float v = acc[0];
 #pragma unroll
@@ -645,29 +587,53 @@ extern "C" int mm_gae(const float* reward, const float* value, const uint8_t* do
     return mm_gae_ex(reward, value, done, last_value, T, N, gamma, gamma_lambda, adv, rtg, MM_GAE_AUTO, stream);
 }
 
+static bool act_mode_ok(int mode) { return mode == MM_ACT_SAMPLE || mode == MM_ACT_GREEDY; }
+
+extern "C" int mm_act(const float* move_logits, const float* mark_logits, const uint8_t* masks, int M, int mode,
+                      uint64_t seed, uint64_t offset, int8_t* actions, float* logp, float* joint_logp, void* stream) {
+    if (!move_logits || !mark_logits || !masks || !actions || M < 0 || !act_mode_ok(mode)) return MM_E_ARG;
+    if (M == 0) return 0;
+    const int nm = (M + 1) / 2;
+    const dim3 grid((nm + 255) / 256), block(256);
+    if (mode == MM_ACT_GREEDY)
+        hipLaunchKernelGGL(k_act<MM_ACT_GREEDY>, grid, block, 0, (hipStream_t)stream, move_logits, mark_logits, masks,
+                           M, seed, offset, actions, logp, joint_logp);
+    else
+        hipLaunchKernelGGL(k_act<MM_ACT_SAMPLE>, grid, block, 0, (hipStream_t)stream, move_logits, mark_logits, masks,
+                           M, seed, offset, actions, logp, joint_logp);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_head_act(const float* h, int ldh, int K, const float* w, const float* b, const uint8_t* masks,
+                           int M, int mode, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                           int8_t* actions, float* logp, float* joint_logp, float* logits, void* stream) {
+    if (!h || !w || !b || !masks || !actions || M < 0 || K <= 0 || (K & 3) || K > kHsMaxK || ldh < K || (ldh & 3) ||
+        ((uintptr_t)h & 15) || !act_mode_ok(mode))
+        return MM_E_ARG;
+    if (M == 0) return 0;
+    const dim3 grid((M + kHsRows - 1) / kHsRows), block(kHsLanes * kHsRows);
+    if (mode == MM_ACT_GREEDY)
+        hipLaunchKernelGGL(k_head_act<MM_ACT_GREEDY>, grid, block, 0, (hipStream_t)stream, h, ldh, K, w, b, masks, M,
+                           seed, offset, offset_dev, actions, logp, joint_logp, logits);
+    else
+        hipLaunchKernelGGL(k_head_act<MM_ACT_SAMPLE>, grid, block, 0, (hipStream_t)stream, h, ldh, K, w, b, masks, M,
+                           seed, offset, offset_dev, actions, logp, joint_logp, logits);
+    return (int)hipGetLastError();
+}
+
+// the sampler's entry points: the same operand checks, the MM_ACT_SAMPLE instantiation
 extern "C" int mm_sample(const float* move_logits, const float* mark_logits, const uint8_t* masks, int M,
                          uint64_t seed, uint64_t offset, int8_t* actions, float* logp, float* joint_logp,
                          void* stream) {
-    if (!move_logits || !mark_logits || !masks || !actions || M < 0) return MM_E_ARG;
-    if (M == 0) return 0;
-    const int nm = (M + 1) / 2;
-    hipLaunchKernelGGL(k_sample, dim3((nm + 255) / 256), dim3(256), 0, (hipStream_t)stream, move_logits, mark_logits,
-                       masks, M, seed, offset, actions, logp, joint_logp);
-    return (int)hipGetLastError();
+    return mm_act(move_logits, mark_logits, masks, M, MM_ACT_SAMPLE, seed, offset, actions, logp, joint_logp, stream);
 }
 
 extern "C" int mm_head_sample_ex(const float* h, int ldh, int K, const float* w, const float* b,
                                  const uint8_t* masks, int M, uint64_t seed, uint64_t offset,
                                  const uint64_t* offset_dev, int8_t* actions, float* logp, float* joint_logp,
                                  float* logits, void* stream) {
-    if (!h || !w || !b || !masks || !actions || M < 0 || K <= 0 || (K & 3) || K > kHsMaxK || ldh < K || (ldh & 3) ||
-        ((uintptr_t)h & 15))
-        return MM_E_ARG;
-    if (M == 0) return 0;
-    hipLaunchKernelGGL(k_head_sample, dim3((M + kHsRows - 1) / kHsRows), dim3(kHsLanes * kHsRows), 0,
-                       (hipStream_t)stream, h, ldh, K, w, b, masks, M, seed, offset, offset_dev, actions, logp,
-                       joint_logp, logits);
-    return (int)hipGetLastError();
+    return mm_head_act(h, ldh, K, w, b, masks, M, MM_ACT_SAMPLE, seed, offset, offset_dev, actions, logp, joint_logp,
+                       logits, stream);
 }
 
 extern "C" int mm_head_sample(const float* h, int ldh, int K, const float* w, const float* b, const uint8_t* masks,

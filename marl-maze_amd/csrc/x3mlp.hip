@@ -876,7 +876,7 @@ struct TrunkArgs {
     int lda, ldc, M, K0;
     int N[3];
     int bx;  // uint16 offset of the second activation buffer (bufH) from the first (bufX)
-    // the fused heads + sampler (k_trunk3<.., HS = true>: k_head_sample's arithmetic on the LDS-resident h3)
+    // the fused heads + sampler (k_trunk3<.., HS = true>: k_head_act's arithmetic on the LDS-resident h3)
     const float* hw;  // [6, N2] = [move_head.weight; mark_head.weight]
     const float* hb;  // [6]
     const uint8_t* masks;
@@ -1091,9 +1091,9 @@ __device__ __forceinline__ void trunk_layer(const uint16_t* src, int K, const ui
 }
 
 // HS: the actor's heads + the action draw fused after the last layer (PPO.py:170-186 with networks.py:38-41):
-// k_head_sample's per-row arithmetic -- 8 lanes a row, the same fma order and butterfly, sample_row -- on the
-// unit's h3 rows in LDS, so the draws, log-probs and logits equal the unfused trunk + k_head_sample's bit for
-// bit; h3 is then written to HBM only when asked (ta.out)
+// k_head_act's per-row code (heads_row_dot, heads_butterfly, heads_finish<MM_ACT_SAMPLE>: policy_device.h) on the unit's h3
+// rows in LDS, so the draws, log-probs and logits equal the unfused trunk + k_head_act's bit for bit; h3 is
+// then written to HBM only when asked (ta.out)
 template <int P, int RT, int D, bool HS>
 __global__ __launch_bounds__(64 * kTrWaves) void k_trunk3(TrunkArgs ta) {
     constexpr int np = Prec<P>::kPlanes;
@@ -1152,7 +1152,7 @@ __global__ __launch_bounds__(64 * kTrWaves) void k_trunk3(TrunkArgs ta) {
             for (int l = 0; l < 3; l++) sbias[kTrMaxN * l + threadIdx.x] = bv[l];
         }
         asm volatile("" ::"v"(boff));
-        if constexpr (HS) {  // the head weights [6, N2], flat (k_head_sample's layout)
+        if constexpr (HS) {  // the head weights [6, N2], flat (row pitch N2, as k_head_act's)
             const __amdgpu_buffer_rsrc_t wrs =
                 __builtin_amdgcn_make_buffer_rsrc((void*)ta.hw, (short)0, 4 * 6 * ta.N[2], 0x00020000);
             uint32_t woff[kHw];
@@ -1199,53 +1199,17 @@ __global__ __launch_bounds__(64 * kTrWaves) void k_trunk3(TrunkArgs ta) {
     trunk_layer<P, RT, D>(bufX, ta.N[1], ta.w[2], ta.N[2], sbias + 2 * kTrMaxN, nullptr, slice, h3s, ta, m0, wave,
                           lane, rm, 6);
     range_note<P>(rm);
-    if constexpr (HS) {  // k_head_sample's body on the LDS rows: 8 lanes a row, 16 RT rows (waves 0 .. 2 RT - 1)
+    if constexpr (HS) {  // the heads' row code on the LDS rows: 8 lanes a row, 16 RT rows (waves 0 .. 2 RT - 1)
         __syncthreads();
-        constexpr int kL = 8;
-        const int K = ta.N[2], sh = K + 4;
-        if (threadIdx.x < kL * 16 * RT) {  // wave-uniform
-            const int j = threadIdx.x % kL, rl = threadIdx.x / kL, row = m0 + rl;
+        const int K = ta.N[2];
+        if (threadIdx.x < kHeadLanes * 16 * RT) {  // wave-uniform
+            const int j = threadIdx.x % kHeadLanes, rl = threadIdx.x / kHeadLanes, row = m0 + rl;  // (m0 is even)
             const bool valid = row < ta.M;
             float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                const float* hr = h3s + rl * sh;
-                for (int c = 4 * j; c < K; c += 4 * kL) {
-                    const float4 hv = *reinterpret_cast<const float4*>(hr + c);
-#pragma unroll
-                    for (int o = 0; o < 6; o++) {
-                        const float4 wv = *reinterpret_cast<const float4*>(shw + o * K + c);
-                        acc[o] = fmaf(hv.x, wv.x, acc[o]);
-                        acc[o] = fmaf(hv.y, wv.y, acc[o]);
-                        acc[o] = fmaf(hv.z, wv.z, acc[o]);
-                        acc[o] = fmaf(hv.w, wv.w, acc[o]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 0; o < 6; o++) {
-#pragma unroll
-                for (int d = kL / 2; d > 0; d >>= 1) acc[o] += __shfl_xor(acc[o], d);
-            }
-            float lp = 0.f;
-            if (valid && j == 0) {
-                float l[5];
-#pragma unroll
-                for (int o = 0; o < 5; o++) l[o] = acc[o] + ta.hb[o];
-                const float kl = acc[5] + ta.hb[5];
-                int move, mark;
-                const uint64_t off = ta.offset + (ta.offset_dev ? *ta.offset_dev : 0ull);
-                lp = sample_row(l, kl, ta.masks + (size_t)row * MM_MASK_DIM, row, ta.seed, off, move, mark);
-                ta.act[2 * row] = (int8_t)move;
-                ta.act[2 * row + 1] = (int8_t)mark;
-                if (ta.logp) ta.logp[row] = lp;
-                if (ta.logits) {
-#pragma unroll
-                    for (int o = 0; o < 5; o++) ta.logits[(size_t)row * 6 + o] = l[o];
-                    ta.logits[(size_t)row * 6 + 5] = kl;
-                }
-            }
-            const float other = __shfl_down(lp, kL);  // rows 2i, 2i + 1: adjacent 8-lane groups (m0 even)
-            if (ta.joint && valid && j == 0 && (row & 1) == 0) ta.joint[row >> 1] = lp + (row + 1 < ta.M ? other : 0.f);
+            if (valid) heads_row_dot(h3s + rl * (K + 4), K, shw, K, j, acc);
+            heads_butterfly(acc);
+            heads_finish<MM_ACT_SAMPLE>(acc, ta.hb, ta.masks, row, ta.M, valid && j == 0, ta.seed, ta.offset,
+                                        ta.offset_dev, ta.act, ta.logp, ta.joint, ta.logits);
         }
     }
     TR_STAMP(7, __builtin_amdgcn_s_memtime());

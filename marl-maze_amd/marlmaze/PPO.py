@@ -327,7 +327,7 @@ class PPO:
             else:
                 b["val"][t] = self.critic(obs_t).view(n)
             # actor trunk, heads and sampling (PPO.py:170-186): one launch after the front-end at small N
-            # (Actor.sample_actions), else the trunk's GEMMs + ops.head_sample
+            # (Actor.sample_actions), else the trunk's GEMMs + ops.head_act (Actor.act)
             self.actor.sample_actions(obs_t.view(2 * n, 65), head_w, head_b, b["masks"][t].view(2 * n, 6),
                                       self.sample_seed, t if offset_dev is not None else self._sample_offset,
                                       actions=b["act"][t].view(2 * n, 2), logp=b["rowlogp"][t],

@@ -371,7 +371,7 @@ def _g16(prec, hs, ws, need_dx):
 
 
 def _heads_fwd(h, wh, bh):
-    """The heads (networks.py:38-41): mm_heads_fwd, fp32 FMA per row with mm_head_sample's arithmetic (the
+    """The heads (networks.py:38-41): mm_heads_fwd, fp32 FMA per row with mm_head_act's arithmetic (the
     rollout's logits, bit for bit), a streaming GEMV over h.  Other head counts: the x3 GEMM."""
     from . import _lib, x3
 
@@ -601,9 +601,9 @@ class Actor(nn.Module):
     def sample_actions(self, x, head_w, head_b, masks, seed, offset, actions, logp=None, joint_logp=None,
                        offset_dev=None):
         """The rollout's actor step (PPO.py:170-186): front-end, trunk, heads and the action draws
-        (ops.head_sample's).  At <= _trunk_max_rows(prec) rows without autograd the trunk, heads and draws run as
-        ONE launch (mm_trunk3_head_sample, bit-identical to trunk + ops.head_sample)."""
-        from . import ops, x3
+        (ops.head_act's, mode "sample").  At <= _trunk_max_rows(prec) rows without autograd the trunk, heads and
+        draws run as ONE launch (mm_trunk3_head_sample, bit-identical to ``act`` in mode "sample")."""
+        from . import x3
 
         h0 = self._front(x)
         M = h0.shape[0]
@@ -616,17 +616,21 @@ class Actor(nn.Module):
                                       masks.to(torch.uint8).contiguous(), seed, offset, actions, logp, joint_logp,
                                       offset_dev=offset_dev)
                 return actions, logp, joint_logp
-        return ops.head_sample(self._mlp(h0), head_w, head_b, masks, seed, offset, actions=actions, logp=logp,
-                               joint_logp=joint_logp, offset_dev=offset_dev)
+        return self.act(None, head_w, head_b, masks, "sample", seed, offset, actions, logp, joint_logp, offset_dev,
+                        h0=h0)
 
     def act(self, x, head_w, head_b, masks, mode="greedy", seed=0, offset=0, actions=None, logp=None,
-            joint_logp=None):
-        """Evaluation's actor step: front-end, trunk (_mlp) and ops.head_act -- ``mode`` "greedy" (the most
-        likely action, no draws) or "sample" (sample_actions' draws at the same seed and offset)."""
+            joint_logp=None, offset_dev=None, h0=None):
+        """The unfused actor step (evaluation's, and the rollout's where the fused launch does not apply):
+        front-end (or its output ``h0``, where the caller has it), trunk (_mlp) and ops.head_act -- ``mode``
+        "greedy" (the most likely action, no draws) or "sample" (sample_actions' draws at the same seed, offset
+        and offset_dev)."""
         from . import ops
 
-        return ops.head_act(self._mlp(self._front(x)), head_w, head_b, masks, mode=mode, seed=seed, offset=offset,
-                            actions=actions, logp=logp, joint_logp=joint_logp)
+        if h0 is None:
+            h0 = self._front(x)
+        return ops.head_act(self._mlp(h0), head_w, head_b, masks, mode=mode, seed=seed, offset=offset,
+                            actions=actions, logp=logp, joint_logp=joint_logp, offset_dev=offset_dev)
 
     def _front(self, x):
         """Projection + attention (networks.py:31-34)."""

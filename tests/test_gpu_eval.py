@@ -2,11 +2,13 @@
 (mm_eval_init, mm_eval_accum) and PPO.evaluate on top of them.
 
 * the greedy head is torch.argmax / (logit > 0) on mm_heads_fwd's logits, exactly;
-* the sampling mode is the old sampler, bit for bit;
+* the sampler, in its plain and its mode form, gives the recorded outputs of tests/golden/sampler_pinned.npz, bit
+  for bit;
 * the totals equal a plain numpy loop, word for word;
 * PPO.evaluate's recorded actions, replayed on the C oracle, give the same episodes and totals;
 * training does not notice an evaluation; greedy evaluation is reproducible; DP sums; the command line.
 """
+import hashlib
 import json
 import os
 import random
@@ -29,6 +31,7 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL, ATOL = 1e-5, 1e-6  # tests/test_gpu_rl.py::test_sampler_logp_and_legality's bar
 SHAPES = [(M, K) for M in (1, 2, 31, 33, 4097) for K in (8, 264)]
+DIGEST_ONLY = {(4097, 264)}  # sampler_pinned.npz holds this shape's arrays as SHA-256 digests (size)
 
 
 def _agent(**kw):
@@ -133,26 +136,48 @@ def test_greedy_head_is_argmax(M, K):
     assert np.array_equal(jl2, (lp2[:, 0] + lp2[:, 1]).astype(np.float32), equal_nan=True)
 
 
+def _pinned(fx, M, K, name, got):
+    """`got` against the recorded array (tests/golden/record_sampler.py): bitwise, NaN (the no-legal-move row)
+    equal to NaN; for a DIGEST_ONLY shape against the recorded SHA-256 of its bytes."""
+    want = fx[f"{M}x{K}/{name}"]
+    got = got.cpu().numpy() if torch.is_tensor(got) else got
+    if (M, K) in DIGEST_ONLY:
+        return np.array_equal(np.frombuffer(hashlib.sha256(np.ascontiguousarray(got).tobytes()).digest(), np.uint8),
+                              want)
+    return got.dtype == want.dtype and np.array_equal(got, want, equal_nan=got.dtype.kind == "f")
+
+
 @pytest.mark.parametrize("M,K", SHAPES)
-def test_sample_mode_is_the_old_sampler(M, K):
-    h, w, b, mk = _head_inputs(M, K)
-    dh, dw, db = (torch.as_tensor(x).cuda() for x in (h, w, b))
-    dmk = torch.as_tensor(mk.astype(np.uint8)).cuda()
+def test_sample_mode_is_the_old_sampler(golden, M, K):
+    """The plain form (ops.head_sample, ops.sample) and the mode form (ops.head_act, ops.act with mode="sample")
+    both give what the sampler gave before the two were one kernel: tests/golden/sampler_pinned.npz."""
+    fx = golden("sampler_pinned")
+    if (M, K) in DIGEST_ONLY:  # the inputs are not in the file: rebuilt, and checked against their digests
+        h, w, b, mk = _head_inputs(M, K)
+        mk = mk.astype(np.uint8)
+        assert all(_pinned(fx, M, K, n, x) for n, x in (("h", h), ("w", w), ("b", b), ("mk", mk))), \
+            "_head_inputs no longer builds the recorded inputs (numpy's generator?): re-record"
+    else:
+        h, w, b, mk = (fx[f"{M}x{K}/{n}"] for n in ("h", "w", "b", "mk"))
+    dh, dw, db, dmk = (torch.as_tensor(x).cuda() for x in (h, w, b, mk))
     off_dev = torch.tensor([3], dtype=torch.int64, device="cuda")
-    for od in (None, off_dev):
+    for tag, od in (("hs", None), ("hsd", off_dev)):
         lg0 = torch.full((M, 6), float("nan"), device="cuda")
         lg1 = torch.full((M, 6), float("nan"), device="cuda")
-        a0, lp0, jl0 = ops.head_sample(dh, dw, db, dmk, 11, 5, logits=lg0, offset_dev=od)
-        a1, lp1, jl1 = ops.head_act(dh, dw, db, dmk, mode="sample", seed=11, offset=5, logits=lg1, offset_dev=od)
-        assert torch.equal(a0, a1) and torch.equal(lg0, lg1)
-        assert np.array_equal(lp0.cpu().numpy(), lp1.cpu().numpy(), equal_nan=True)
-        assert np.array_equal(jl0.cpu().numpy(), jl1.cpu().numpy(), equal_nan=True)
-    # and the logits-input pair
-    z = _heads_fwd(dh, dw, db)
-    s0 = ops.sample(z[:, :5], z[:, 5], dmk, 11, 5)
-    s1 = ops.act(z[:, :5], z[:, 5], dmk, mode="sample", seed=11, offset=5)
-    for x, y in zip(s0, s1):
-        assert np.array_equal(x.cpu().numpy(), y.cpu().numpy(), equal_nan=True)
+        r0 = ops.head_sample(dh, dw, db, dmk, 11, 5, logits=lg0, offset_dev=od)
+        r1 = ops.head_act(dh, dw, db, dmk, mode="sample", seed=11, offset=5, logits=lg1, offset_dev=od)
+        for r, lg in ((r0, lg0), (r1, lg1)):
+            assert _pinned(fx, M, K, "hs_logits", lg)
+            for n, x in zip(("a", "lp", "jl"), r):
+                assert _pinned(fx, M, K, f"{tag}_{n}", x), (tag, n)
+    # and the logits-input pair, on those logits
+    s0 = ops.sample(lg0[:, :5], lg0[:, 5], dmk, 11, 5)
+    s1 = ops.act(lg0[:, :5], lg0[:, 5], dmk, mode="sample", seed=11, offset=5)
+    for s in (s0, s1):
+        for n, x in zip(("a", "lp", "jl"), s):
+            assert _pinned(fx, M, K, f"s_{n}", x), n
+    if M > 2:  # the forced rows are there: the no-legal-move row is NaN, and the device offset moved the draws
+        assert np.isnan(s0[1].cpu().numpy()[3]) and not torch.equal(r0[0], s0[0])
 
 
 # ---------------------------------------------------------------------------
