@@ -546,6 +546,49 @@ int mm_eval_init(uint64_t* totals, int32_t* counted, int n, void* stream);
 int mm_eval_accum(const uint8_t* done, const float* reward, const int32_t* ep_stats, int n, int quota,
                   int32_t* counted, uint64_t* totals, void* stream);
 
+/* Distance fields and the par time of every maze (csrc/solve_kernels.hip): one wavefront per maze, a
+ * level-synchronous breadth-first search over the maze's layout staged in LDS.
+ * Passable: (cell & 3) != 1 (marks can be walked over); with marks_block != 0: (cell & 3) == 0 (the rule of the
+ * reference's Maze.get_shortest_path, maze.py:261-273, which this generalises to every cell at once).
+ * mm_env_dist: dist [n, layout_stride] int16; row i is the distance field of the target cell targets[i] = (x, y) of
+ * maze i, row-major with the maze's own width (index y * w + x): the number of moves on the 4-neighbour grid from
+ * the cell to the target through passable cells.  The target itself is 0 whenever it lies inside the grid,
+ * whatever its value (an impassable target reaches nothing else); -1 marks walls, unreachable cells and every entry
+ * at or beyond w * h.  A target outside the grid, w * h == 0 (a maze that was seeded but never reset) or
+ * w * h > layout_stride give a row of -1.
+ * mm_env_par: par [n, 4] int32 = {par, fetcher, d(s_f, key) + d(key, end), d(s_o, end)} of the maze as it stands
+ * right after a reset: agent 0 starts on (sx, sy), agent 1 on spawn1; for a fetcher f and the other agent o,
+ * cand(f) = max(d(s_f, key) + d(key, end), d(s_o, end)); par = min(cand(0), cand(1)), fetcher its arg-min (agent
+ * 0 wins a tie).  The shortest possible solving episode (maze.py:115-119: done with reward 1 needs the key and both
+ * agents on the end cell).  Marks do not block.  No key (kx < 0) or a needed distance of -1: all four are -1.
+ * select (both calls; [n] uint8 or NULL = all): the rows of mazes with select[i] == 0 are left untouched. */
+int mm_env_dist(const mm_env_t* env, const int16_t* targets, const uint8_t* select, int marks_block, int16_t* dist,
+                void* stream);
+int mm_env_par(const mm_env_t* env, const uint8_t* select, int32_t* par, void* stream);
+
+/* Totals of exit time against par over an evaluation run (csrc/solve_kernels.hip): totals [MM_PAR_WORDS] uint64
+ * and counted [n] int32 on the device; integer words, exact and independent of the workgroup order, as
+ * mm_eval_init / mm_eval_accum.
+ * mm_par_init: counted = 0, totals = 0.
+ * mm_par_accum (after every env step, with mm_env_par's rows of the mazes that were stepped): every maze m with
+ * done[m] != 0 and counted[m] < quota has counted[m] incremented (mm_eval_accum's rule, on an array of its own);
+ * when the episode is solved (reward[m] == 1.0f), len = ep_stats[2 m] is rated against p = par[4 m]. */
+#define MM_PAR_WORDS 32
+#define MM_PAR_EPISODES 0        /* counted solved episodes with p > 0 ("rated") */
+#define MM_PAR_SUM_LEN 1         /* sum of len over rated episodes */
+#define MM_PAR_SUM_PAR 2         /* sum of p over rated episodes */
+#define MM_PAR_SUM_RATIO_Q16 3   /* sum of floor(len * 65536 / p) over rated episodes */
+#define MM_PAR_AT_PAR 4          /* rated episodes with len == p */
+#define MM_PAR_BELOW 5           /* rated episodes with len < p: always 0 unless something is broken */
+#define MM_PAR_UNRATED 6         /* counted solved episodes with p <= 0 */
+#define MM_PAR_MAX_EXCESS 7      /* max of len - p over rated episodes (0: none above par) */
+/* (words 8..15: zero) */
+#define MM_PAR_HIST0 16          /* words 16..31: histogram over rated episodes, bin */
+#define MM_PAR_HIST_BINS 16      /* clamp(4 * len / p - 4, 0, 15) (integer division), the last bin open */
+int mm_par_init(uint64_t* totals, int32_t* counted, int n, void* stream);
+int mm_par_accum(const uint8_t* done, const float* reward, const int32_t* ep_stats, const int32_t* par, int n,
+                 int quota, int32_t* counted, uint64_t* totals, void* stream);
+
 /* The critic's value in one launch (networks.py:87-102, inference: PPO.get_batch's per-step
  * self.critic(obs), PPO.py:111): v [M] = w2 . ReLU(w1 ReLU(w0 x + b0) + b1) + b2 for x [M, K0] (row
  * stride ldx), w0 [H0, K0], w1 [H1, H0], w2 [1, H1] (nn.Linear layouts), on the fp32 MFMA (exact fmaf

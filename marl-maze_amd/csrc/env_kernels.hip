@@ -23,8 +23,6 @@
 #include "marlmaze.h"
 #include "mt19937_wave.h"
 
-extern "C" int mm_layout_stride(int size_w, int size_h, int rand_sizes, int rand_lo, int rand_hi);
-
 namespace mm {
 
 constexpr int kMaxCells = MM_MAX_SIDE * MM_MAX_SIDE;
@@ -822,24 +820,6 @@ static int cu_count() {
     if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         cus[dev] = 256;
     return cus[dev];
-}
-
-inline int check_env(const mm_env_t* env) {
-    if (!env || env->n <= 0 || !env->layout || !env->agents || !env->mazes || !env->rng || !env->work) return MM_E_ARG;
-    const int need = mm_layout_stride(env->size_w, env->size_h, env->rand_sizes, env->rand_lo, env->rand_hi);
-    if (need < 0 || env->size_w < 2 || env->size_h < 2) return MM_E_SIZE;
-    if (env->rand_sizes && (env->rand_lo < 2 || env->rand_hi < env->rand_lo)) return MM_E_SIZE;
-    if (env->layout_stride < need) return MM_E_SIZE;
-    // k_step stages the layouts by 16-byte LDS-DMA; the state records are 32-byte structs
-    if ((reinterpret_cast<uintptr_t>(env->layout) | reinterpret_cast<uintptr_t>(env->agents) |
-         reinterpret_cast<uintptr_t>(env->mazes)) & 15)
-        return MM_E_ARG;
-    if (env->difficulty < 1 || env->max_timestep < 1) return MM_E_ARG;
-    const int npg = !!env->next_layout + !!env->next_mazes + !!env->next_rng + !!env->gen_state;
-    if (npg != 0 && npg != 4) return MM_E_ARG;  // the pre-generation buffers come as a set
-    if ((reinterpret_cast<uintptr_t>(env->next_layout) | reinterpret_cast<uintptr_t>(env->next_mazes)) & 15)
-        return MM_E_ARG;
-    return 0;
 }
 
 }  // namespace mm

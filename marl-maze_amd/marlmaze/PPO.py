@@ -764,7 +764,7 @@ class PPO:
     # ------------------------------------------------------------------
     @torch.no_grad()
     def evaluate(self, episodes_per_env=1, greedy=True, n_envs=None, env_config=None, seed_base=0, eval_seed=0,
-                 poll=16, record=False):
+                 poll=16, record=False, par=False):
         """How good is the policy: ``episodes_per_env`` whole episodes on each of ``n_envs`` fresh mazes
         (seeds ``seed_base + rank n + i``; configuration ``env_config``, else this agent's), every agent
         taking its most likely action (``greedy``) or drawing one (Philox key ``eval_seed``, counter = the
@@ -774,6 +774,11 @@ class PPO:
         ``episodes_per_env * max_timestep`` steps, where an episode is cut off.  Under DP the totals are those
         of all ranks' mazes.
 
+        ``par``: also rate every counted solved episode against the par time of its maze, the length of the
+        shortest possible solving episode (VecMaze.par; mm_par_accum after mm_eval_accum, then mm_env_par for
+        the mazes that finished and hold their next maze); the result gains marlmaze.evaluate.
+        result_from_par_words' keys.  Off (the default), nothing is launched and nothing is added.
+
         Returns marlmaze.evaluate.result_from_words' dict plus ``env_steps`` and ``seconds``; with ``record``
         also a dict of the per-step ``actions`` [T, n, 2, 2], ``done`` [T, n] and ``reward`` [T, n] of this
         rank (for small n).  Training does not notice the call: it uses an environment and buffers of its own
@@ -782,7 +787,7 @@ class PPO:
         import time
 
         from . import _lib
-        from .evaluate import NONE_MIN, result_from_words
+        from .evaluate import NONE_MIN, result_from_par_words, result_from_words
 
         n, E = int(n_envs if n_envs is not None else self.n_envs), int(episodes_per_env)
         if n < 1 or E < 1:
@@ -792,7 +797,7 @@ class PPO:
         dev, dp = self.device, self.dp
         seeds = np.arange(n, dtype=np.uint64) + np.uint64(int(seed_base) + dp.rank * n)
         args = (n, E, seeds, kw, "greedy" if greedy else "sample", int(eval_seed) + 7919 * dp.rank,
-                max(1, int(poll)), bool(record))
+                max(1, int(poll)), bool(record), bool(par))
 
         # The fp16-plane GEMMs (x2, f16) raise the library's range flag, which belongs to the rollout and the
         # update (_range_guarded).  It is only looked at here, never cleared while it carries their state: raised
@@ -810,7 +815,7 @@ class PPO:
             if guarded and flag_anywhere()[1]:
                 self.actor.gemm_prec = "x3"
                 guarded = False
-            T, words, rec, t0 = self._eval_run(*args)
+            T, words, pwords, rec, t0 = self._eval_run(*args)
             if guarded:
                 mine, anywhere = flag_anywhere()
                 if anywhere:
@@ -819,7 +824,7 @@ class PPO:
                     warnings.warn(f"marlmaze: a {prec} GEMM operand of the evaluation reached |x| >= 2^15 (fp16 "
                                   "planes): the evaluation is repeated at x3")
                     self.actor.gemm_prec = "x3"
-                    T, words, rec, t0 = self._eval_run(*args)
+                    T, words, pwords, rec, t0 = self._eval_run(*args)
             seconds = time.perf_counter() - t0
         finally:
             self.actor.gemm_prec = prec
@@ -832,19 +837,27 @@ class PPO:
             ext = dp.allreduce_max(ext).tolist()
             words[_lib.EV_MAX_LEN_SOLVED] = ext[0]
             words[_lib.EV_MIN_LEN_SOLVED] = 2**62 - ext[1] if ext[1] > 0 else NONE_MIN
+            if pwords is not None:  # sums, and the max of the one extreme word
+                pw = dp.allreduce_sum(torch.tensor([0 if k == _lib.PAR_MAX_EXCESS else v for k, v in enumerate(pwords)],
+                                                   dtype=torch.int64, device=dev)).tolist()
+                pw[_lib.PAR_MAX_EXCESS] = int(dp.allreduce_max(torch.tensor([pwords[_lib.PAR_MAX_EXCESS]],
+                                                                            dtype=torch.int64, device=dev)))
+                pwords = pw
         res = result_from_words(words)
+        if pwords is not None:
+            res.update(result_from_par_words(pwords))
         res["env_steps"] = n * T * dp.world
         res["seconds"] = seconds
         return (res, rec) if record else res
 
-    def _eval_run(self, n, E, seeds, kw, mode, key, poll, record):
+    def _eval_run(self, n, E, seeds, kw, mode, key, poll, record, par=False):
         """One evaluation at the actor's current GEMM precision on a fresh VecMaze: (steps, this rank's 32 words,
-        the recorded steps or None, the stepping loop's start time).  The side-stream maze pre-generation is
+        its 32 words against par or None, the recorded steps or None, the stepping loop's start time).  The side-stream maze pre-generation is
         queued once per poll window, as the rollout queues it once per horizon (VecMaze.defer_pregen)."""
         import time
 
         from . import _lib
-        from .evaluate import EvalTotals
+        from .evaluate import EvalTotals, ParTotals
 
         dev, dp = self.device, self.dp
         venv = VecMaze(n, seeds=seeds, device=dev, **kw)
@@ -860,6 +873,10 @@ class PPO:
         head_w, head_b = self.actor.heads()
         rec = dict(actions=[], done=[], reward=[]) if record else None
         venv.reset(obs=obs, masks=masks)
+        partot = parbuf = None
+        if par:  # every maze's par time, refreshed below whenever a maze is replaced by its next one
+            partot = ParTotals(n, E, device=dev)
+            parbuf = venv.par()
         torch.cuda.synchronize(dev)  # the caller's `seconds` is the stepping loop's: the mazes exist
         t0, t = time.perf_counter(), 0
         venv.defer_pregen = True
@@ -870,6 +887,9 @@ class PPO:
                                    actions=act.view(2 * n, 2), logp=rowlp)
                     venv.step(act, auto_reset=True, obs=obs, masks=masks, reward=rew, done=done, ep_stats=stats)
                     tot.accum(done, rew, stats)
+                    if par:  # the par of the maze that just finished, then that of the maze the reset installed
+                        partot.accum(done, rew, stats, parbuf)
+                        venv.par(select=done, out=parbuf)
                     t += 1
                     if rec is not None:
                         rec["actions"].append(act.clone())
@@ -893,7 +913,7 @@ class PPO:
             venv._quiesce_pregen()  # the side stream's generation ends before the buffers go
         if rec is not None:
             rec = {k: torch.stack(v) for k, v in rec.items()}
-        return t, words, rec, t0
+        return t, words, (partot.words() if par else None), rec, t0
 
     def train(self, eval_every=0, eval_kwargs=None):
         """PPO.train (PPO.py:22-44).  ``eval_every`` > 0: after every ``eval_every``-th epoch, evaluate(**eval_kwargs)

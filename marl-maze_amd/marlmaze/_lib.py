@@ -32,6 +32,11 @@ EV_EPISODES, EV_SOLVED, EV_TIMEOUTS, EV_SUM_LEN, EV_SUM_LEN_SOLVED, EV_SUM_SHORT
 EV_MIN_LEN_SOLVED, EV_MAX_LEN_SOLVED, EV_SUM_RATIO_Q16, EV_BAD_SHORT = 6, 7, 8, 9
 EV_HIST0, EV_HIST_BINS = 16, 16
 
+PAR_WORDS = 32  # MM_PAR_WORDS: uint64 words of an evaluation's totals against par (mm_par_init, mm_par_accum)
+PAR_EPISODES, PAR_SUM_LEN, PAR_SUM_PAR, PAR_SUM_RATIO_Q16, PAR_AT_PAR, PAR_BELOW = 0, 1, 2, 3, 4, 5  # MM_PAR_*
+PAR_UNRATED, PAR_MAX_EXCESS = 6, 7
+PAR_HIST0, PAR_HIST_BINS = 16, 16
+
 AF_KNOWS_END = 1
 AF_SEES_END = 2
 AF_OTHER_KNOWS = 4
@@ -55,7 +60,8 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_gemm_range_flag", "mm_gemm_nt_h", "mm_gemm_a16_ok", "mm_gemm_wgrad_h", "mm_gemm_wgrad_partials_h",
            "mm_heads_fwd_h16", "mm_x3_heads_bwd_h16", "mm_trunk3_ok", "mm_trunk3",
            "mm_trunk3_head_sample_ok", "mm_trunk3_head_sample", "mm_actor_front_fwd_h16",
-           "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum")
+           "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum",
+           "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum")
 VERSION = 308  # mm_version() this binding is written for
 
 PREC_X3, PREC_F16, PREC_X2 = 0, 1, 2  # MM_PREC_*
@@ -167,6 +173,14 @@ def lib():
         L.mm_eval_init.restype = i32
         L.mm_eval_accum.argtypes = [P, P, P, i32, i32, P, P, P]
         L.mm_eval_accum.restype = i32
+        L.mm_env_dist.argtypes = [ctypes.POINTER(EnvDesc), P, P, i32, P, P]
+        L.mm_env_dist.restype = i32
+        L.mm_env_par.argtypes = [ctypes.POINTER(EnvDesc), P, P, P]
+        L.mm_env_par.restype = i32
+        L.mm_par_init.argtypes = [P, P, i32, P]
+        L.mm_par_init.restype = i32
+        L.mm_par_accum.argtypes = [P, P, P, P, i32, i32, P, P, P]
+        L.mm_par_accum.restype = i32
         L.mm_x3_tp_len.argtypes = [i32, i32]
         L.mm_x3_tp_len.restype = ctypes.c_long
         L.mm_x3_tp_pack.argtypes = [P, i32, i32, i32, i32, P, P]

@@ -128,10 +128,48 @@ class Maze:
         return 0 <= x < self.width and 0 <= y < self.height
 
     def get_shortest_path(self, start, end):
-        """maze.py:261-273 (the path through the tree; start/end must be this maze's)."""
-        if tuple(start) != self.start or tuple(end) != self.end:
-            raise NotImplementedError("only the start -> end path of the current maze is kept on the device")
-        return list(self.shortest_path)
+        """maze.py:261-273: the cells from ``start`` to ``end`` inclusive, ``[start]`` when they are equal, None
+        when there is no path.  Only cells equal to 0 can be entered (a marked cell blocks, maze.py:270).  The
+        current maze's own (start, end) is the stored path; any other pair takes the distance field of ``start``
+        from the device (VecMaze.distance_field, marks_block) and descends it from ``end``."""
+        start, end = (int(start[0]), int(start[1])), (int(end[0]), int(end[1]))
+        if self._env is not None and start == self.start and end == self.end and self.shortest_path is not None:
+            return list(self.shortest_path)
+        if start == end:
+            return [start]
+        if self._env is None or not (self.is_valid_cell(*start) and self.is_valid_cell(*end)):
+            return None
+        if self._env.layouts()[0][start[1], start[0]] == 0:
+            return self._descend(start, end)
+        # the reference expands ``start`` whatever its value (a marked cell an agent stands on): the path leaves
+        # it through one of its free neighbours and cannot come back (last pushed first, maze.py:265)
+        for dx, dy in reversed(DELTAS):
+            nb = (start[0] + dx, start[1] + dy)
+            if self.is_valid_cell(*nb) and self._env.layouts()[0][nb[1], nb[0]] == 0:
+                rest = self._descend(nb, end)
+                if rest is not None:
+                    return [start] + rest
+        return None
+
+    def _descend(self, start, end):
+        """The path start -> end over cells equal to 0 (start itself is one), from the device's distance field."""
+        w = self.width
+        field = self._env.distance_field(np.asarray([start], np.int16), marks_block=True)[0].cpu().numpy()
+        d = int(field[end[1] * w + end[0]])
+        if d < 0:
+            return None
+        path = [end]
+        x, y = end
+        while d > 0:  # a neighbour one move nearer to start
+            for dx, dy in DELTAS:
+                nx, ny = x + dx, y + dy
+                if self.is_valid_cell(nx, ny) and int(field[ny * w + nx]) == d - 1:
+                    x, y, d = nx, ny, d - 1
+                    break
+            else:
+                return None
+            path.append((x, y))
+        return path[::-1]
 
     # ---- the viewer (maze.py:276-522), headless: marlmaze.viewer ----
     def draw_maze(self, id=-1):

@@ -223,6 +223,66 @@ class VecMaze:
         self._kick_pregen()  # mazes whose next maze was pending at the snapshot
 
     # ------------------------------------------------------------------
+    # solver: distance fields and par times (csrc/solve_kernels.hip)
+    # ------------------------------------------------------------------
+    _RECORD_TARGETS = {"end": 6, "key": 8, "start": 10}  # byte offset of the (x, y) pair in mm_maze_t
+
+    def _select(self, select):
+        if select is None:
+            return None
+        s = torch.as_tensor(select)
+        if s.numel() != self.n:
+            raise ValueError(f"select: {self.n} entries expected, got {s.numel()}")
+        if s.dtype != torch.uint8:
+            s = s != 0
+        return s.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def _out(self, out, shape, dtype, what):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if out.dtype != dtype or tuple(out.shape) != shape or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous {dtype} {list(shape)} tensor on {self.device}")
+        return out
+
+    def distance_field(self, targets="end", select=None, marks_block=False, out=None):
+        """int16 [n, stride]: row i holds, for every cell of maze i (index y * w + x with the maze's own width),
+        the number of moves to the target cell through passable cells -- 0 at the target, -1 on walls, on
+        unreachable cells and at or beyond w * h (mm_env_dist).
+
+        targets: "end", "key" (an all -1 row once the key is gone) or "start", the cells of the mazes' own
+        records as they stand on the stream; or an [n, 2] integer array / tensor of (x, y).
+        marks_block: marked cells block too (the reference's get_shortest_path rule, maze.py:270); by default
+        only walls do.  select ([n], nonzero = compute): the other mazes' rows of ``out`` are left untouched.
+        Stream-ordered: no host synchronisation."""
+        if isinstance(targets, str):
+            if targets not in self._RECORD_TARGETS:
+                raise ValueError(f"targets: one of {sorted(self._RECORD_TARGETS)} or an [n, 2] array")
+            o = self._RECORD_TARGETS[targets]
+            tg = self.mazes[:, o:o + 2].view(torch.int8).to(torch.int16)
+        else:
+            tg = torch.as_tensor(targets)
+            if tg.numel() != 2 * self.n or tg.is_floating_point():
+                raise ValueError(f"targets: an integer [{self.n}, 2] array of (x, y)")
+            tg = tg.reshape(self.n, 2).to(device=self.device, dtype=torch.int16)
+        tg = tg.contiguous()
+        sel = self._select(select)
+        out = self._out(out, (self.n, self.stride), torch.int16, "distance_field")
+        _lib.check(_lib.lib().mm_env_dist(ctypes.byref(self._desc), _lib.ptr(tg), _lib.ptr(sel), int(bool(marks_block)),
+                                          _lib.ptr(out), _lib.stream_ptr()), "mm_env_dist")
+        return out
+
+    def par(self, select=None, out=None):
+        """int32 [n, 4] = (par, fetcher, d(s_f, key) + d(key, end), d(s_o, end)) of every maze as it stands right
+        after a reset (mm_env_par): the length of the shortest possible solving episode, the agent that fetches
+        the key in it, and the two legs.  All -1 for a maze without a key (picked up already, generation failed,
+        never reset).  select and the stream order as distance_field()."""
+        sel = self._select(select)
+        out = self._out(out, (self.n, 4), torch.int32, "par")
+        _lib.check(_lib.lib().mm_env_par(ctypes.byref(self._desc), _lib.ptr(sel), _lib.ptr(out), _lib.stream_ptr()),
+                   "mm_env_par")
+        return out
+
+    # ------------------------------------------------------------------
     # host-side introspection (tests, facades, stats) -- synchronising
     # ------------------------------------------------------------------
     def maze_info(self):
