@@ -15,6 +15,8 @@
  *   mm_gae        PPO.get_GAEs                                  PPO.py:193-203
  *   mm_sample     PPO.get_action (masked Categorical move +     PPO.py:170-186
  *                 Bernoulli mark, joint log-prob)
+ *   mm_elog_*     nothing: one record per finished episode, written   (PPO.get_batch keeps an episode's
+ *                 between the step and the reset                     length only, PPO.py:127-131)
  *
  * Conventions
  *   - Every pointer is a caller-owned DEVICE buffer (e.g. a torch tensor);
@@ -588,6 +590,51 @@ int mm_env_par(const mm_env_t* env, const uint8_t* select, int32_t* par, void* s
 int mm_par_init(uint64_t* totals, int32_t* counted, int n, void* stream);
 int mm_par_accum(const uint8_t* done, const float* reward, const int32_t* ep_stats, const int32_t* par, int n,
                  int quota, int32_t* counted, uint64_t* totals, void* stream);
+
+/* The episode log (csrc/elog_kernels.hip): one record of MM_ELOG_WORDS int32 per finished episode, written on the
+ * device where the episode ran -- which maze, how it ended, when the key was found and by whom, when each agent
+ * learnt the exit, when the team became exit-ready, how much of the maze each agent covered.  Replaces nothing in
+ * the reference (its PPO.get_batch keeps an episode's length and nothing else, PPO.py:127-131).
+ * The finished maze's state is overwritten by its reset, so the log sits between the two: per env step
+ *   mm_env_step(..., auto_reset = 2);  mm_elog_step;  mm_env_reset_done;  mm_elog_start(select = done)
+ * and mm_elog_start(select = NULL) after the first mm_env_reset.
+ * Buffers (caller-owned, int32): log [n, quota, MM_ELOG_WORDS] (16-byte aligned), counted [n], state
+ * [n * state_words] with state_words = mm_elog_state_words(layout_stride): two visit bitmaps of
+ * ceil(layout_stride / 32) words plus the scalars, per maze.  The state's layout is the library's own (word-major:
+ * word k of maze m at state[k * n + m]); callers keep it between calls and do not interpret it.
+ * mm_elog_init: log = -1 everywhere, counted = 0, state = 0.
+ * mm_elog_start: for every maze with select[m] != 0 (select [n] uint8, NULL = all), right after its reset: clears its
+ *   running state, enters the agents' cells (their spawn cells) into the bitmaps, sets T_KNOW* to 0 where the
+ *   reset's observation already set MM_AF_KNOWS_END, and counts OPEN over the layout's w * h bytes.  The other mazes'
+ *   state is left untouched.
+ * mm_elog_step: for every maze, from the agents, the maze and the actions [n,2,2] as they stand after the step: the
+ *   cells stood on, the milestones (t = mm_maze_t.t after the step), the marks and stays.  Then, with the step's done
+ *   [n], reward [n], ep_stats [n,2] (8-byte aligned) and par [n,4] (mm_env_par's rows, or NULL): every maze with
+ *   done[m] != 0 and counted[m] < quota has its record written at log[m, counted[m]] and counted[m] incremented
+ *   (mm_eval_accum's quota rule, on an array of its own); episodes past the quota write nothing. */
+#define MM_ELOG_WORDS 16
+#define MM_ELOG_LEN 0          /* ep_stats[2 m]: the episode's length */
+#define MM_ELOG_SHORTEST 1     /* ep_stats[2 m + 1]: shortest_path_len */
+#define MM_ELOG_SOLVED 2       /* 1 if reward[m] == 1.0f, 0 if the episode timed out */
+#define MM_ELOG_PAR 3          /* par[4 m], -1 without a par buffer */
+#define MM_ELOG_T_KEY 4        /* t of the first step after which the key is gone (kx < 0); -1 if never */
+#define MM_ELOG_FETCHER 5      /* the agent (0 / 1) holding MM_AF_HAS_KEY at that step; -1 if never (or neither) */
+#define MM_ELOG_T_KNOW0 6      /* first t at which agent 0 has MM_AF_KNOWS_END; 0 from the reset's observation; */
+#define MM_ELOG_T_KNOW1 7      /* -1 if never.  The same for agent 1 */
+#define MM_ELOG_T_READY 8      /* first t at which both agents have KNOWS_END and TEAM_KEY (maze.py:106); -1 if never */
+#define MM_ELOG_CELLS0 9       /* distinct cells agent 0 has stood on, its spawn cell included */
+#define MM_ELOG_CELLS1 10      /* ... agent 1 */
+#define MM_ELOG_CELLS_BOTH 11  /* cells both agents have stood on */
+#define MM_ELOG_OPEN 12        /* cells with (cell & 3) != 1 at the episode's start */
+#define MM_ELOG_MARKS0 13      /* steps in which agent 0's action had mark == 1 (the action bytes as given) */
+#define MM_ELOG_MARKS1 14      /* ... agent 1's */
+#define MM_ELOG_STAYS 15       /* (agent, step) pairs with move == 4 */
+long mm_elog_state_words(int layout_stride);
+int mm_elog_init(int32_t* log, int32_t* counted, int32_t* state, int n, int quota, long state_words, void* stream);
+int mm_elog_start(const mm_env_t* env, const uint8_t* select, int32_t* state, long state_words, void* stream);
+int mm_elog_step(const mm_env_t* env, const int8_t* actions, const uint8_t* done, const float* reward,
+                 const int32_t* ep_stats, const int32_t* par, int quota, int32_t* counted, int32_t* state,
+                 long state_words, int32_t* log, void* stream);
 
 /* The critic's value in one launch (networks.py:87-102, inference: PPO.get_batch's per-step
  * self.critic(obs), PPO.py:111): v [M] = w2 . ReLU(w1 ReLU(w0 x + b0) + b1) + b2 for x [M, K0] (row

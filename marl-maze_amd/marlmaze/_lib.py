@@ -37,6 +37,13 @@ PAR_EPISODES, PAR_SUM_LEN, PAR_SUM_PAR, PAR_SUM_RATIO_Q16, PAR_AT_PAR, PAR_BELOW
 PAR_UNRATED, PAR_MAX_EXCESS = 6, 7
 PAR_HIST0, PAR_HIST_BINS = 16, 16
 
+ELOG_WORDS = 16  # MM_ELOG_WORDS: int32 words of one episode record (mm_elog_init, mm_elog_start, mm_elog_step)
+ELOG_LEN, ELOG_SHORTEST, ELOG_SOLVED, ELOG_PAR, ELOG_T_KEY, ELOG_FETCHER, ELOG_T_KNOW0, ELOG_T_KNOW1 = range(8)  # MM_ELOG_*
+ELOG_T_READY, ELOG_CELLS0, ELOG_CELLS1, ELOG_CELLS_BOTH, ELOG_OPEN, ELOG_MARKS0, ELOG_MARKS1, ELOG_STAYS = range(8, 16)
+# the record's fields in word order (the names of marlmaze.evaluate.EpisodeLog.records())
+ELOG_FIELDS = ("LEN", "SHORTEST", "SOLVED", "PAR", "T_KEY", "FETCHER", "T_KNOW0", "T_KNOW1", "T_READY", "CELLS0",
+               "CELLS1", "CELLS_BOTH", "OPEN", "MARKS0", "MARKS1", "STAYS")
+
 AF_KNOWS_END = 1
 AF_SEES_END = 2
 AF_OTHER_KNOWS = 4
@@ -61,7 +68,8 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_heads_fwd_h16", "mm_x3_heads_bwd_h16", "mm_trunk3_ok", "mm_trunk3",
            "mm_trunk3_head_sample_ok", "mm_trunk3_head_sample", "mm_actor_front_fwd_h16",
            "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum",
-           "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum")
+           "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum",
+           "mm_elog_state_words", "mm_elog_init", "mm_elog_start", "mm_elog_step")
 VERSION = 308  # mm_version() this binding is written for
 
 PREC_X3, PREC_F16, PREC_X2 = 0, 1, 2  # MM_PREC_*
@@ -181,6 +189,14 @@ def lib():
         L.mm_par_init.restype = i32
         L.mm_par_accum.argtypes = [P, P, P, P, i32, i32, P, P, P]
         L.mm_par_accum.restype = i32
+        L.mm_elog_state_words.argtypes = [i32]
+        L.mm_elog_state_words.restype = ctypes.c_long
+        L.mm_elog_init.argtypes = [P, P, P, i32, i32, ctypes.c_long, P]
+        L.mm_elog_init.restype = i32
+        L.mm_elog_start.argtypes = [ctypes.POINTER(EnvDesc), P, P, ctypes.c_long, P]
+        L.mm_elog_start.restype = i32
+        L.mm_elog_step.argtypes = [ctypes.POINTER(EnvDesc), P, P, P, P, P, i32, P, P, ctypes.c_long, P, P]
+        L.mm_elog_step.restype = i32
         L.mm_x3_tp_len.argtypes = [i32, i32]
         L.mm_x3_tp_len.restype = ctypes.c_long
         L.mm_x3_tp_pack.argtypes = [P, i32, i32, i32, i32, P, P]
