@@ -568,7 +568,7 @@ int mm_env_dist(const mm_env_t* env, const int16_t* targets, const uint8_t* sele
                 void* stream);
 int mm_env_par(const mm_env_t* env, const uint8_t* select, int32_t* par, void* stream);
 
-/* Totals of exit time against par over an evaluation run (csrc/solve_kernels.hip): totals [MM_PAR_WORDS] uint64
+/* Totals of exit time against par over an evaluation run (csrc/eval_kernels.hip): totals [MM_PAR_WORDS] uint64
  * and counted [n] int32 on the device; integer words, exact and independent of the workgroup order, as
  * mm_eval_init / mm_eval_accum.
  * mm_par_init: counted = 0, totals = 0.

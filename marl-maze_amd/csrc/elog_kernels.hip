@@ -27,6 +27,7 @@
 
 #include "env_device.h"
 #include "marlmaze.h"
+#include "quota_device.h"
 
 namespace mm {
 
@@ -164,10 +165,10 @@ __global__ __launch_bounds__(kElThreads) void k_elog_step(mm_env_t env, const ch
     if (mk1) S[kElMarks1 * N] = marks1 + 1;
     if (st) S[kElStays * N] = stays + st;
     if (dn == 0) return;
-    // the episode ended with this step: its record, if the maze still has quota (mm_eval_accum's rule)
-    const int32_t c = counted[m];
-    if (c >= quota) return;
-    counted[m] = c + 1;
+    // the episode ended with this step: its record, if the maze still has quota (quota_device.h; `counted` is
+    // read here, after the running state's stores, and only by the lanes whose episode ended)
+    const int32_t c = quota_claim(dn, counted, m, quota);
+    if (c < 0) return;
     int n0 = 0, n1 = 0, nb = 0;
     for (int k = 0; k < bw; k++) {
         const uint32_t b0 = (uint32_t)S[(size_t)(kElScalars + k) * N], b1 = (uint32_t)S[(size_t)(kElScalars + bw + k) * N];

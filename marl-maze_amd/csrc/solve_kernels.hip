@@ -12,9 +12,8 @@
 //               The search ends at the first empty frontier, at the latest after w * h levels.
 //   k_env_par   the same search for two targets at once, the end and the key (two fields in LDS, one barrier pair
 //               per level for both), then a handful of reads at the two spawn cells and the key: the par time of
-//               the maze (marlmaze.h).  The fields are not written out.
-//   k_par_init / k_par_accum  integer totals of exit time against par, one thread per maze, with k_eval_accum's
-//               reduction: wavefront shuffles, LDS atomics, one global atomic per non-empty word.
+//               the maze (marlmaze.h).  The fields are not written out.  (The totals of exit time against these
+//               par times are an evaluation's: k_par_accum in eval_kernels.hip.)
 //
 // The number of levels differs from maze to maze.  A workgroup is one wavefront, so __syncthreads() is local to
 // the wavefront of one maze and a maze that finishes early cannot strand a barrier that another still waits at.
@@ -216,98 +215,6 @@ __global__ __launch_bounds__(64) void k_env_par(mm_env_t env, const uint8_t* __r
     }
 }
 
-// ---------------------------------------------------------------------------
-// totals of exit time against par
-// ---------------------------------------------------------------------------
-typedef unsigned long long u64;
-constexpr int kParThreads = 256;
-
-__global__ void k_par_init(u64* __restrict__ totals, int32_t* __restrict__ counted, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) counted[i] = 0;
-    if (i < MM_PAR_WORDS) totals[i] = 0ull;
-}
-
-__device__ __forceinline__ u64 par_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-
-__global__ __launch_bounds__(kParThreads) void k_par_accum(const uint8_t* __restrict__ done,
-                                                           const float* __restrict__ reward,
-                                                           const int2* __restrict__ ep_stats,
-                                                           const int32_t* __restrict__ par, int n, int quota,
-                                                           int32_t* __restrict__ counted, u64* __restrict__ totals) {
-    __shared__ u64 s[MM_PAR_HIST0];                  // the scalar words of this workgroup
-    __shared__ unsigned int hist[MM_PAR_HIST_BINS];  // (<= 256 episodes per workgroup and launch)
-    const int tid = threadIdx.x, m = blockIdx.x * kParThreads + tid;
-    if (tid < MM_PAR_HIST0) s[tid] = 0ull;
-    if (tid < MM_PAR_HIST_BINS) hist[tid] = 0u;
-    __syncthreads();
-    bool ev = false;
-    if (m < n && done[m] != 0) {
-        const int32_t c = counted[m];
-        if (c < quota) {
-            counted[m] = c + 1;
-            ev = reward[m] == 1.0f;  // only solved episodes are rated
-        }
-    }
-    if (__any(ev)) {  // wave-uniform: most waves of most steps hold no solved episode
-        u64 rated = 0, len = 0, sp = 0, ratio = 0, at = 0, below = 0, unrated = 0, mx = 0;
-        if (ev) {
-            const int l = ep_stats[m].x, p = par[4 * (size_t)m];
-            if (p <= 0) {
-                unrated = 1;
-            } else {
-                rated = 1;
-                len = (u64)(int64_t)l;
-                sp = (u64)p;
-                ratio = (len << 16) / (u64)p;  // floor(len 65536 / p)
-                at = l == p;
-                below = l < p;
-                mx = l > p ? (u64)(l - p) : 0ull;
-                const int64_t bin = 4 * (int64_t)l / (int64_t)p - 4;
-                atomicAdd(&hist[bin < 0 ? 0 : bin > MM_PAR_HIST_BINS - 1 ? MM_PAR_HIST_BINS - 1 : (int)bin], 1u);
-            }
-        }
-        rated = par_wave_sum(rated);
-        len = par_wave_sum(len);
-        sp = par_wave_sum(sp);
-        ratio = par_wave_sum(ratio);
-        at = par_wave_sum(at);
-        below = par_wave_sum(below);
-        unrated = par_wave_sum(unrated);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const u64 b = __shfl_down(mx, d);
-            mx = b > mx ? b : mx;
-        }
-        if ((tid & 63) == 0) {
-            atomicAdd(&s[MM_PAR_EPISODES], rated);
-            atomicAdd(&s[MM_PAR_SUM_LEN], len);
-            atomicAdd(&s[MM_PAR_SUM_PAR], sp);
-            atomicAdd(&s[MM_PAR_SUM_RATIO_Q16], ratio);
-            atomicAdd(&s[MM_PAR_AT_PAR], at);
-            atomicAdd(&s[MM_PAR_BELOW], below);
-            atomicAdd(&s[MM_PAR_UNRATED], unrated);
-            atomicMax(&s[MM_PAR_MAX_EXCESS], mx);
-        }
-    }
-    __syncthreads();
-    // one global atomic per word that this workgroup changed
-    if (tid < MM_PAR_HIST0) {
-        const u64 v = s[tid];
-        if (v != 0) {
-            if (tid == MM_PAR_MAX_EXCESS) atomicMax(&totals[tid], v);
-            else atomicAdd(&totals[tid], v);
-        }
-    } else if (tid < MM_PAR_WORDS) {
-        const unsigned int v = hist[tid - MM_PAR_HIST0];
-        if (v != 0) atomicAdd(&totals[tid], (u64)v);
-    }
-}
-
 constexpr int kSolveGrid = 1 << 16;  // workgroups (mazes in flight); more mazes take turns
 
 }  // namespace mm
@@ -330,26 +237,5 @@ extern "C" int mm_env_par(const mm_env_t* env, const uint8_t* select, int32_t* p
     if (!par || ((uintptr_t)par & 3)) return MM_E_ARG;
     hipLaunchKernelGGL(k_env_par, dim3(env->n < kSolveGrid ? env->n : kSolveGrid), dim3(64),
                        solve_lds_bytes<2>(solve_cap(env->layout_stride)), (hipStream_t)stream, *env, select, par);
-    return (int)hipGetLastError();
-}
-
-extern "C" int mm_par_init(uint64_t* totals, int32_t* counted, int n, void* stream) {
-    if (!totals || !counted || n < 0 || ((uintptr_t)totals & 7) || ((uintptr_t)counted & 3)) return MM_E_ARG;
-    const int threads = n > MM_PAR_WORDS ? n : MM_PAR_WORDS;
-    hipLaunchKernelGGL(k_par_init, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<u64*>(totals), counted, n);
-    return (int)hipGetLastError();
-}
-
-extern "C" int mm_par_accum(const uint8_t* done, const float* reward, const int32_t* ep_stats, const int32_t* par,
-                            int n, int quota, int32_t* counted, uint64_t* totals, void* stream) {
-    if (!done || !reward || !ep_stats || !par || !counted || !totals || n < 0 || quota < 0 ||
-        ((uintptr_t)reward & 3) || ((uintptr_t)ep_stats & 7) || ((uintptr_t)par & 3) || ((uintptr_t)counted & 3) ||
-        ((uintptr_t)totals & 7))
-        return MM_E_ARG;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_par_accum, dim3((n + kParThreads - 1) / kParThreads), dim3(kParThreads), 0,
-                       (hipStream_t)stream, done, reward, reinterpret_cast<const int2*>(ep_stats), par, n, quota,
-                       counted, reinterpret_cast<u64*>(totals));
     return (int)hipGetLastError();
 }

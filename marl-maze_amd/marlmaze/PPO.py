@@ -762,198 +762,16 @@ class PPO:
     # ------------------------------------------------------------------
     # evaluation
     # ------------------------------------------------------------------
-    @torch.no_grad()
     def evaluate(self, episodes_per_env=1, greedy=True, n_envs=None, env_config=None, seed_base=0, eval_seed=0,
                  poll=16, record=False, par=False, episode_log=False):
-        """How good is the policy: ``episodes_per_env`` whole episodes on each of ``n_envs`` fresh mazes
-        (seeds ``seed_base + rank n + i``; configuration ``env_config``, else this agent's), every agent
-        taking its most likely action (``greedy``) or drawing one (Philox key ``eval_seed``, counter = the
-        step).  Per step: front-end, trunk, mm_head_act, the env step with auto-reset, mm_eval_accum; the
-        totals are read every ``poll`` steps and the run ends when every maze has contributed its episodes
-        (each maze its first ``episodes_per_env``, see marlmaze.evaluate) -- at the latest after
-        ``episodes_per_env * max_timestep`` steps, where an episode is cut off.  Under DP the totals are those
-        of all ranks' mazes.
+        """How good is the policy: ``episodes_per_env`` whole episodes on each of ``n_envs`` fresh mazes, greedy or
+        sampled, counted on the device; optionally rated against par and logged per episode.  Returns the result
+        dict (with ``record``: and the recorded steps).  Training does not notice the call.  The arguments, the
+        result and the driver itself: marlmaze.evaluate.evaluate_policy."""
+        from .evaluate import evaluate_policy
 
-        ``par``: also rate every counted solved episode against the par time of its maze, the length of the
-        shortest possible solving episode (VecMaze.par; mm_par_accum after mm_eval_accum, then mm_env_par for
-        the mazes that finished and hold their next maze); the result gains marlmaze.evaluate.
-        result_from_par_words' keys.  Off (the default), nothing is launched and nothing is added.
-
-        ``episode_log``: also write one record per counted episode on the device (marlmaze.evaluate.EpisodeLog:
-        which maze, the outcome and par, when the key was found and by whom, when each agent learnt the exit, when
-        the team became exit-ready, the cells covered, marks and stays).  The finished mazes' state is gone once
-        they are reset, so the step becomes: the env step with its finished mazes only queued (auto_reset=2),
-        mm_eval_accum, mm_par_accum, mm_elog_step, the queued resets, mm_elog_start and mm_env_par for the mazes that
-        finished -- the same mazes, actions and totals as without it.  The result gains ``episode_log``, this rank's
-        records as a numpy structured array (EpisodeLog.records() plus ``seed``, the maze's seed; PAR is -1 without
-        ``par``), and ``behaviour``, marlmaze.evaluate.behaviour_from_sums' statistics over all ranks' records.  Off
-        (the default), the step is the one above, nothing is launched and nothing is added.
-
-        Returns marlmaze.evaluate.result_from_words' dict plus ``env_steps`` and ``seconds``; with ``record``
-        also a dict of the per-step ``actions`` [T, n, 2, 2], ``done`` [T, n] and ``reward`` [T, n] of this
-        rank (for small n).  Training does not notice the call: it uses an environment and buffers of its own
-        and leaves the rollout's environment, buffers, sampler offset, the range-guard state and every random
-        generator as they are."""
-        import time
-
-        from . import _lib
-        from .evaluate import (BEHAVIOUR_SUMS, NONE_MIN, behaviour_from_sums, behaviour_sums, result_from_par_words,
-                               result_from_words)
-
-        n, E = int(n_envs if n_envs is not None else self.n_envs), int(episodes_per_env)
-        if n < 1 or E < 1:
-            raise ValueError("evaluate needs n_envs >= 1 and episodes_per_env >= 1")
-        kw = dict(env_config) if env_config is not None else self._env_kwargs()
-        kw.pop("seed_base", None)
-        dev, dp = self.device, self.dp
-        seeds = np.arange(n, dtype=np.uint64) + np.uint64(int(seed_base) + dp.rank * n)
-        args = (n, E, seeds, kw, "greedy" if greedy else "sample", int(eval_seed) + 7919 * dp.rank,
-                max(1, int(poll)), bool(record), bool(par), bool(episode_log))
-
-        # The fp16-plane GEMMs (x2, f16) raise the library's range flag, which belongs to the rollout and the
-        # update (_range_guarded).  It is only looked at here, never cleared while it carries their state: raised
-        # already -> this run uses x3 (which leaves it alone); raised BY this run -> back to clear, its state
-        # before, and the run is repeated at x3, as the update does.  Under DP both decisions are taken from the
-        # MAX over ranks (_range_flags' rule): every rank runs at the same precision and issues the same
-        # collectives
-        def flag_anywhere():
-            mine = x3.range_flag(clear=False)
-            return bool(int(mine)), bool(int(dp.allreduce_max(mine.clone())))
-
-        guarded = self.flat is not None and self.actor.gemm_prec != "x3"
-        prec = self.actor.gemm_prec
-        try:
-            if guarded and flag_anywhere()[1]:
-                self.actor.gemm_prec = "x3"
-                guarded = False
-            T, words, pwords, rec, t0, erec = self._eval_run(*args)
-            if guarded:
-                mine, anywhere = flag_anywhere()
-                if anywhere:
-                    if mine:  # raised by this run (it was clear before): clear again
-                        x3.range_flag(clear=True)
-                    warnings.warn(f"marlmaze: a {prec} GEMM operand of the evaluation reached |x| >= 2^15 (fp16 "
-                                  "planes): the evaluation is repeated at x3")
-                    self.actor.gemm_prec = "x3"
-                    T, words, pwords, rec, t0, erec = self._eval_run(*args)
-            seconds = time.perf_counter() - t0
-        finally:
-            self.actor.gemm_prec = prec
-        if dp.active:  # sums, and max / min (as the max of a complement) of the two extreme words
-            mn, mx = words[_lib.EV_MIN_LEN_SOLVED], words[_lib.EV_MAX_LEN_SOLVED]
-            w = torch.tensor([0 if k == _lib.EV_MIN_LEN_SOLVED else v for k, v in enumerate(words)],
-                             dtype=torch.int64, device=dev)
-            ext = torch.tensor([mx, 2**62 - mn if mn != NONE_MIN else 0], dtype=torch.int64, device=dev)
-            words = dp.allreduce_sum(w).tolist()
-            ext = dp.allreduce_max(ext).tolist()
-            words[_lib.EV_MAX_LEN_SOLVED] = ext[0]
-            words[_lib.EV_MIN_LEN_SOLVED] = 2**62 - ext[1] if ext[1] > 0 else NONE_MIN
-            if pwords is not None:  # sums, and the max of the one extreme word
-                pw = dp.allreduce_sum(torch.tensor([0 if k == _lib.PAR_MAX_EXCESS else v for k, v in enumerate(pwords)],
-                                                   dtype=torch.int64, device=dev)).tolist()
-                pw[_lib.PAR_MAX_EXCESS] = int(dp.allreduce_max(torch.tensor([pwords[_lib.PAR_MAX_EXCESS]],
-                                                                            dtype=torch.int64, device=dev)))
-                pwords = pw
-        res = result_from_words(words)
-        if pwords is not None:
-            res.update(result_from_par_words(pwords))
-        if erec is not None:  # this rank's records; the statistics from one summed vector of all ranks' integers
-            sums = behaviour_sums(erec)
-            if dp.active:
-                sums = dp.allreduce_sum(torch.tensor([sums[k] for k in BEHAVIOUR_SUMS], dtype=torch.int64,
-                                                     device=dev)).tolist()
-            res["episode_log"] = erec
-            res["behaviour"] = behaviour_from_sums(sums)
-        res["env_steps"] = n * T * dp.world
-        res["seconds"] = seconds
-        return (res, rec) if record else res
-
-    def _eval_run(self, n, E, seeds, kw, mode, key, poll, record, par=False, episode_log=False):
-        """One evaluation at the actor's current GEMM precision on a fresh VecMaze: (steps, this rank's 32 words,
-        its 32 words against par or None, the recorded steps or None, the stepping loop's start time, its episode
-        records or None).  The side-stream maze pre-generation is
-        queued once per poll window, as the rollout queues it once per horizon (VecMaze.defer_pregen)."""
-        import time
-
-        from . import _lib
-        from .evaluate import EpisodeLog, EvalTotals, ParTotals
-
-        dev, dp = self.device, self.dp
-        venv = VecMaze(n, seeds=seeds, device=dev, **kw)
-        max_steps = E * venv.max_timestep  # k_step ends an episode at t >= max_timestep
-        obs = torch.empty((n, 2, 65), dtype=torch.float32, device=dev)
-        masks = torch.empty((n, 2, 6), dtype=torch.uint8, device=dev)
-        act = torch.empty((n, 2, 2), dtype=torch.int8, device=dev)
-        rowlp = torch.empty(2 * n, dtype=torch.float32, device=dev)
-        rew = torch.empty(n, dtype=torch.float32, device=dev)
-        done = torch.empty(n, dtype=torch.uint8, device=dev)
-        stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
-        tot = EvalTotals(n, E, device=dev)
-        head_w, head_b = self.actor.heads()
-        rec = dict(actions=[], done=[], reward=[]) if record else None
-        venv.reset(obs=obs, masks=masks)
-        partot = parbuf = None
-        if par:  # every maze's par time, refreshed below whenever a maze is replaced by its next one
-            partot = ParTotals(n, E, device=dev)
-            parbuf = venv.par()
-        elog = None
-        if episode_log:  # the first episodes' spawn cells and open cells
-            elog = EpisodeLog(venv, E)
-            elog.start()
-        torch.cuda.synchronize(dev)  # the caller's `seconds` is the stepping loop's: the mazes exist
-        t0, t = time.perf_counter(), 0
-        venv.defer_pregen = True
-        try:
-            with x3.cached_packs():  # the weights are fixed: packed once
-                while True:
-                    self.actor.act(obs.view(2 * n, 65), head_w, head_b, masks.view(2 * n, 6), mode, key, t,
-                                   actions=act.view(2 * n, 2), logp=rowlp)
-                    if elog is None:
-                        venv.step(act, auto_reset=True, obs=obs, masks=masks, reward=rew, done=done, ep_stats=stats)
-                        tot.accum(done, rew, stats)
-                        if par:  # the par of the maze that just finished, then that of the maze the reset installed
-                            partot.accum(done, rew, stats, parbuf)
-                            venv.par(select=done, out=parbuf)
-                    else:  # the same step with the log between the finished mazes' last state and their reset
-                        venv.step(act, auto_reset=2, obs=obs, masks=masks, reward=rew, done=done, ep_stats=stats)
-                        tot.accum(done, rew, stats)
-                        if par:
-                            partot.accum(done, rew, stats, parbuf)
-                        elog.step(act, done, rew, stats, parbuf)
-                        venv.reset_done(obs=obs, masks=masks)
-                        elog.start(select=done)
-                        if par:
-                            venv.par(select=done, out=parbuf)
-                    t += 1
-                    if rec is not None:
-                        rec["actions"].append(act.clone())
-                        rec["done"].append(done.clone())
-                        rec["reward"].append(rew.clone())
-                    if t % poll and t < max_steps:
-                        continue
-                    venv.defer_pregen = False  # the window's finished mazes get their next mazes generated
-                    venv.flush_pregen()
-                    venv.defer_pregen = True
-                    words = tot.words()  # the host synchronisation
-                    count = torch.tensor([words[_lib.EV_EPISODES]], dtype=torch.int64, device=dev)
-                    if int(dp.allreduce_sum(count)) == n * E * dp.world:  # every rank stops at the same step
-                        break
-                    if t >= max_steps:
-                        raise RuntimeError(f"evaluate: {int(count)} of {n * E * dp.world} episodes after {t} "
-                                           f"steps (max_timestep {venv.max_timestep})")
-        finally:
-            venv.defer_pregen = False
-            venv.flush_pregen()
-            venv._quiesce_pregen()  # the side stream's generation ends before the buffers go
-        if rec is not None:
-            rec = {k: torch.stack(v) for k, v in rec.items()}
-        erec = None
-        if elog is not None:
-            from numpy.lib import recfunctions
-
-            erec = elog.records()
-            erec = recfunctions.append_fields(erec, "seed", seeds[erec["maze"]], usemask=False)
-        return t, words, (partot.words() if par else None), rec, t0, erec
+        return evaluate_policy(self, episodes_per_env, greedy, n_envs, env_config, seed_base, eval_seed, poll, record,
+                               par, episode_log)
 
     def train(self, eval_every=0, eval_kwargs=None):
         """PPO.train (PPO.py:22-44).  ``eval_every`` > 0: after every ``eval_every``-th epoch, evaluate(**eval_kwargs)

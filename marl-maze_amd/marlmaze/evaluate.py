@@ -7,27 +7,35 @@ exit time over shortest path).  Every maze contributes its FIRST ``quota`` episo
 result is a per-maze average: without the quota, mazes with short episodes would finish more of them inside
 any fixed number of steps and bias the success rate upwards.
 
-``ParTotals`` is its counterpart against par (mm_par_init / mm_par_accum, csrc/solve_kernels.hip): the exit time of
-every counted solved episode over the par time of its maze, the length of the shortest possible solving episode
-(VecMaze.par).  The floor of that ratio is 1.0, which the ratio over the shortest start -> end path cannot reach:
-the key never lies on that path.
+``ParTotals`` is its counterpart against par (mm_par_init / mm_par_accum, the same file and the same 32-word
+shape): the exit time of every counted solved episode over the par time of its maze, the length of the shortest
+possible solving episode (VecMaze.par).  The floor of that ratio is 1.0, which the ratio over the shortest
+start -> end path cannot reach: the key never lies on that path.
 
 ``EpisodeLog`` keeps what the totals cannot say: one record per counted episode (mm_elog_init / mm_elog_start /
 mm_elog_step, csrc/elog_kernels.hip) -- which maze, its outcome and par, when the key was found and by whom, when
 each agent learnt the exit, when the team became exit-ready, the cells each agent covered, its marks and stays.
 ``behaviour_sums`` / ``behaviour_from_sums`` reduce the records to statistics, each a ratio of two integer sums.
 
-``PPO.evaluate`` drives all three; ``python -m marlmaze.evaluate --model PPO.pth ...`` is the command line.
+``evaluate_policy`` drives all three (``PPO.evaluate`` is a call of it): the look at the GEMMs' range flag and
+the repeat at x3, the stepping loop (``_run``, one step sequence with or without par and the log), the reduction
+of the words over DP ranks (``reduce_words``, from the tables EVAL_EXTREMES / PAR_EXTREMES) and the result dict.
+``python -m marlmaze.evaluate --model PPO.pth ...`` is the command line.
 """
 import argparse
+import collections
 import ctypes
 import json
 import sys
+import time
+import warnings
 
 import numpy as np
 import torch
+from numpy.lib import recfunctions
 
-from . import _lib
+from . import _lib, x3
+from .vecmaze import VecMaze
 
 NONE_MIN = 2**64 - 1  # the min word before any solved episode
 RATIO_BIN_EDGES = [1.0 + 0.25 * k for k in range(_lib.EV_HIST_BINS)]  # lower edges; the last bin is open
@@ -67,11 +75,29 @@ def result_from_par_words(words):
         par_hist=w[_lib.PAR_HIST0:_lib.PAR_HIST0 + _lib.PAR_HIST_BINS], par_bin_edges=list(PAR_BIN_EDGES))
 
 
-class EvalTotals:
-    """Device totals of an evaluation over ``n`` mazes, ``quota`` episodes per maze.
+def _check_step_args(who, n, done, reward, ep_stats, par=None, actions=None):
+    """ValueError unless one env step's tensors are what the accumulate kernels read for ``n`` mazes: done [n]
+    uint8, reward [n] float32, ep_stats [n, 2] int32 and, where given, par [n, 4] int32 and actions [n, 2, 2] int8,
+    each contiguous.  Called before anything is launched (and once per step: one flat condition)."""
+    if (done.dtype != torch.uint8 or reward.dtype != torch.float32 or ep_stats.dtype != torch.int32
+            or done.numel() != n or reward.numel() != n or ep_stats.numel() != 2 * n
+            or not (done.is_contiguous() and reward.is_contiguous() and ep_stats.is_contiguous())
+            or (par is not None and (par.dtype != torch.int32 or par.numel() != 4 * n or not par.is_contiguous()))
+            or (actions is not None and (actions.dtype != torch.int8 or actions.numel() != 4 * n
+                                         or not actions.is_contiguous()))):
+        raise ValueError(f"{who}: done [n] uint8, reward [n] float32, ep_stats [n, 2] int32 and, where taken, par "
+                         "[n, 4] int32 and actions [n, 2, 2] int8, contiguous")
+
+
+class _Totals:
+    """32 uint64 words of totals on the device over ``n`` mazes, ``quota`` episodes per maze, with the ``counted``
+    array of the quota rule.  A subclass names its mm_*_init entry point, gives the result function of its words
+    and adds accum().
 
     init() and accum() are stream-ordered launches (no allocation, no synchronisation); words() and read()
     copy the 32 words to the host."""
+
+    _init = _result = None
 
     def __init__(self, n, quota=1, device=None):
         if device is None:
@@ -82,66 +108,43 @@ class EvalTotals:
         self.init()
 
     def init(self):
-        _lib.check(_lib.lib().mm_eval_init(_lib.ptr(self.totals), _lib.ptr(self.counted), self.n, _lib.stream_ptr()),
-                   "mm_eval_init")
+        _lib.check(getattr(_lib.lib(), self._init)(_lib.ptr(self.totals), _lib.ptr(self.counted), self.n,
+                                                   _lib.stream_ptr()), self._init)
+
+    def words(self):
+        """The 32 words as python ints (uint64).  Synchronises."""
+        return [int(v) & (2**64 - 1) for v in self.totals.tolist()]
+
+    def read(self):
+        return self._result(self.words())
+
+
+class EvalTotals(_Totals):
+    """Device totals of an evaluation over ``n`` mazes, ``quota`` episodes per maze."""
+
+    _init, _result = "mm_eval_init", staticmethod(result_from_words)
 
     def accum(self, done, reward, ep_stats):
         """One env step's done [n] u8, reward [n] f32 and ep_stats [n, 2] int32 (VecMaze.step's)."""
-        if (done.dtype != torch.uint8 or reward.dtype != torch.float32 or ep_stats.dtype != torch.int32
-                or done.numel() != self.n or reward.numel() != self.n or ep_stats.numel() != 2 * self.n
-                or not (done.is_contiguous() and reward.is_contiguous() and ep_stats.is_contiguous())):
-            raise ValueError("EvalTotals.accum: done [n] uint8, reward [n] float32, ep_stats [n, 2] int32, contiguous")
+        _check_step_args("EvalTotals.accum", self.n, done, reward, ep_stats)
         _lib.check(_lib.lib().mm_eval_accum(_lib.ptr(done), _lib.ptr(reward), _lib.ptr(ep_stats), self.n, self.quota,
                                             _lib.ptr(self.counted), _lib.ptr(self.totals), _lib.stream_ptr()),
                    "mm_eval_accum")
 
-    def words(self):
-        """The 32 words as python ints (uint64).  Synchronises."""
-        return [int(v) & (2**64 - 1) for v in self.totals.tolist()]
 
-    def read(self):
-        return result_from_words(self.words())
-
-
-class ParTotals:
+class ParTotals(_Totals):
     """Device totals of exit time against par over ``n`` mazes, ``quota`` episodes per maze (EvalTotals' shape,
-    with a ``counted`` array of its own).
+    with a ``counted`` array of its own)."""
 
-    init() and accum() are stream-ordered launches (no allocation, no synchronisation); words() and read()
-    copy the 32 words to the host."""
-
-    def __init__(self, n, quota=1, device=None):
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.n, self.quota = int(n), int(quota)
-        self.totals = torch.empty(_lib.PAR_WORDS, dtype=torch.int64, device=device)  # uint64 words
-        self.counted = torch.empty(self.n, dtype=torch.int32, device=device)
-        self.init()
-
-    def init(self):
-        _lib.check(_lib.lib().mm_par_init(_lib.ptr(self.totals), _lib.ptr(self.counted), self.n, _lib.stream_ptr()),
-                   "mm_par_init")
+    _init, _result = "mm_par_init", staticmethod(result_from_par_words)
 
     def accum(self, done, reward, ep_stats, par):
         """One env step's done [n] u8, reward [n] f32 and ep_stats [n, 2] int32 (VecMaze.step's), and the par
         rows [n, 4] int32 (VecMaze.par's) of the mazes that were stepped."""
-        if (done.dtype != torch.uint8 or reward.dtype != torch.float32 or ep_stats.dtype != torch.int32
-                or par.dtype != torch.int32 or done.numel() != self.n or reward.numel() != self.n
-                or ep_stats.numel() != 2 * self.n or par.numel() != 4 * self.n
-                or not (done.is_contiguous() and reward.is_contiguous() and ep_stats.is_contiguous()
-                        and par.is_contiguous())):
-            raise ValueError("ParTotals.accum: done [n] uint8, reward [n] float32, ep_stats [n, 2] int32, "
-                             "par [n, 4] int32, contiguous")
+        _check_step_args("ParTotals.accum", self.n, done, reward, ep_stats, par)
         _lib.check(_lib.lib().mm_par_accum(_lib.ptr(done), _lib.ptr(reward), _lib.ptr(ep_stats), _lib.ptr(par),
                                            self.n, self.quota, _lib.ptr(self.counted), _lib.ptr(self.totals),
                                            _lib.stream_ptr()), "mm_par_accum")
-
-    def words(self):
-        """The 32 words as python ints (uint64).  Synchronises."""
-        return [int(v) & (2**64 - 1) for v in self.totals.tolist()]
-
-    def read(self):
-        return result_from_par_words(self.words())
 
 
 RECORD_DTYPE = np.dtype([("maze", "<i4"), ("episode", "<i4")] + [(name, "<i4") for name in _lib.ELOG_FIELDS])
@@ -195,16 +198,7 @@ class EpisodeLog:
         """After venv.step(actions, auto_reset=2, ...) and before venv.reset_done(): the step's actions [n, 2, 2]
         int8, done [n] u8, reward [n] f32 and ep_stats [n, 2] int32, and (optional) the par rows [n, 4] int32
         (VecMaze.par's) of the mazes that were stepped."""
-        n = self.n
-        if (actions.dtype != torch.int8 or done.dtype != torch.uint8 or reward.dtype != torch.float32
-                or ep_stats.dtype != torch.int32 or actions.numel() != 4 * n or done.numel() != n
-                or reward.numel() != n or ep_stats.numel() != 2 * n
-                or not (actions.is_contiguous() and done.is_contiguous() and reward.is_contiguous()
-                        and ep_stats.is_contiguous())
-                or (par is not None and (par.dtype != torch.int32 or par.numel() != 4 * n
-                                         or not par.is_contiguous()))):
-            raise ValueError("EpisodeLog.step: actions [n, 2, 2] int8, done [n] uint8, reward [n] float32, ep_stats "
-                             "[n, 2] int32, par [n, 4] int32 or None, contiguous")
+        _check_step_args("EpisodeLog.step", self.n, done, reward, ep_stats, par, actions)
         _lib.check(_lib.lib().mm_elog_step(ctypes.byref(self.venv._desc), _lib.ptr(actions), _lib.ptr(done),
                                            _lib.ptr(reward), _lib.ptr(ep_stats), _lib.ptr(par), self.quota,
                                            _lib.ptr(self.counted), _lib.ptr(self.state), self.state_words,
@@ -274,6 +268,201 @@ def worst_records(records, k, by_par):
     worst first, ties in (maze, episode) order."""
     key = records["LEN"].astype(np.int64) - (np.maximum(records["PAR"], 0) if by_par else 0)
     return records[np.argsort(-key, kind="stable")[:max(0, int(k))]]
+
+
+# The words that are not sums, by kind; every other word of the 32 is a sum.  Nothing else says which is which
+# on the host: reduce_words reads these two tables
+EVAL_EXTREMES = {_lib.EV_MIN_LEN_SOLVED: "min", _lib.EV_MAX_LEN_SOLVED: "max"}
+PAR_EXTREMES = {_lib.PAR_MAX_EXCESS: "max"}
+
+
+def _reduce(words, extremes, dp, device):
+    """One set of 32 words over all ranks, in two collectives: a SUM of the sums and a MAX of the extremes, a
+    minimum travelling as the maximum of its complement (0 from a rank whose min word is still NONE_MIN)."""
+    sums = torch.tensor([0 if k in extremes else v for k, v in enumerate(words)], dtype=torch.int64, device=device)
+    ext = torch.tensor([words[k] if kind == "max" else (2**62 - words[k] if words[k] != NONE_MIN else 0)
+                        for k, kind in extremes.items()], dtype=torch.int64, device=device)
+    out = dp.allreduce_sum(sums).tolist()
+    for (k, kind), v in zip(extremes.items(), dp.allreduce_max(ext).tolist()):
+        out[k] = v if kind == "max" else (2**62 - v if v > 0 else NONE_MIN)
+    return out
+
+
+def reduce_words(words, pwords, dp, device):
+    """This rank's 32 words and its 32 words against par (or None, on every rank alike) -> those of all ranks'
+    mazes.  Every rank issues the same collectives in the same order: two for the totals, then two for par if
+    there is par.  Under DP.single() the input is returned as it is."""
+    if not dp.active:
+        return words, pwords
+    return (_reduce(words, EVAL_EXTREMES, dp, device),
+            None if pwords is None else _reduce(pwords, PAR_EXTREMES, dp, device))
+
+
+# one evaluation run on this rank: the steps taken, its 32 words, its 32 words against par or None, the recorded
+# steps or None, the stepping loop's start time, and its episode records or None
+EvalRun = collections.namedtuple("EvalRun", "steps words pwords record t0 records")
+
+
+def _run(agent, n, E, seeds, kw, mode, key, poll, record, par, episode_log):
+    """One evaluation at the actor's current GEMM precision on a fresh VecMaze -> EvalRun.  The side-stream maze
+    pre-generation is queued once per poll window, as the rollout queues it once per horizon
+    (VecMaze.defer_pregen)."""
+    dev, dp = agent.device, agent.dp
+    venv = VecMaze(n, seeds=seeds, device=dev, **kw)
+    max_steps = E * venv.max_timestep  # k_step ends an episode at t >= max_timestep
+    obs = torch.empty((n, 2, 65), dtype=torch.float32, device=dev)
+    masks = torch.empty((n, 2, 6), dtype=torch.uint8, device=dev)
+    act = torch.empty((n, 2, 2), dtype=torch.int8, device=dev)
+    rowlp = torch.empty(2 * n, dtype=torch.float32, device=dev)
+    rew = torch.empty(n, dtype=torch.float32, device=dev)
+    done = torch.empty(n, dtype=torch.uint8, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    tot = EvalTotals(n, E, device=dev)
+    head_w, head_b = agent.actor.heads()
+    rec = dict(actions=[], done=[], reward=[]) if record else None
+    venv.reset(obs=obs, masks=masks)
+    partot = parbuf = None
+    if par:  # every maze's par time, refreshed below whenever a maze is replaced by its next one
+        partot = ParTotals(n, E, device=dev)
+        parbuf = venv.par()
+    elog = None
+    if episode_log:  # the first episodes' spawn cells and open cells
+        elog = EpisodeLog(venv, E)
+        elog.start()
+    torch.cuda.synchronize(dev)  # the caller's `seconds` is the stepping loop's: the mazes exist
+    t0, t = time.perf_counter(), 0
+    venv.defer_pregen = True
+    try:
+        with x3.cached_packs():  # the weights are fixed: packed once
+            while True:
+                agent.actor.act(obs.view(2 * n, 65), head_w, head_b, masks.view(2 * n, 6), mode, key, t,
+                                actions=act.view(2 * n, 2), logp=rowlp)
+                # with the log, the finished mazes are only queued (auto_reset=2) and reset below, after the log
+                # has seen their last state; without it the step resets them itself, in the same launch
+                venv.step(act, auto_reset=2 if elog else True, obs=obs, masks=masks, reward=rew, done=done,
+                          ep_stats=stats)
+                tot.accum(done, rew, stats)
+                if par:  # against the par of the maze that just finished
+                    partot.accum(done, rew, stats, parbuf)
+                if elog:
+                    elog.step(act, done, rew, stats, parbuf)
+                    venv.reset_done(obs=obs, masks=masks)
+                    elog.start(select=done)
+                if par:  # the par of the maze that the reset installed
+                    venv.par(select=done, out=parbuf)
+                t += 1
+                if rec is not None:
+                    rec["actions"].append(act.clone())
+                    rec["done"].append(done.clone())
+                    rec["reward"].append(rew.clone())
+                if t % poll and t < max_steps:
+                    continue
+                venv.defer_pregen = False  # the window's finished mazes get their next mazes generated
+                venv.flush_pregen()
+                venv.defer_pregen = True
+                words = tot.words()  # the host synchronisation
+                count = torch.tensor([words[_lib.EV_EPISODES]], dtype=torch.int64, device=dev)
+                if int(dp.allreduce_sum(count)) == n * E * dp.world:  # every rank stops at the same step
+                    break
+                if t >= max_steps:
+                    raise RuntimeError(f"evaluate: {int(count)} of {n * E * dp.world} episodes after {t} "
+                                       f"steps (max_timestep {venv.max_timestep})")
+    finally:
+        venv.defer_pregen = False
+        venv.flush_pregen()
+        venv._quiesce_pregen()  # the side stream's generation ends before the buffers go
+    if rec is not None:
+        rec = {k: torch.stack(v) for k, v in rec.items()}
+    erec = None
+    if elog:
+        erec = elog.records()
+        erec = recfunctions.append_fields(erec, "seed", seeds[erec["maze"]], usemask=False)
+    return EvalRun(t, words, partot.words() if par else None, rec, t0, erec)
+
+
+@torch.no_grad()
+def evaluate_policy(agent, episodes_per_env=1, greedy=True, n_envs=None, env_config=None, seed_base=0, eval_seed=0,
+                    poll=16, record=False, par=False, episode_log=False):
+    """How good is the policy of ``agent`` (a PPO; ``PPO.evaluate`` is this function): ``episodes_per_env`` whole
+    episodes on each of ``n_envs`` fresh mazes (seeds ``seed_base + rank n + i``; configuration ``env_config``,
+    else the agent's), every agent taking its most likely action (``greedy``) or drawing one (Philox key
+    ``eval_seed``, counter = the step).  Per step: front-end, trunk, mm_head_act, the env step with auto-reset,
+    mm_eval_accum; the totals are read every ``poll`` steps and the run ends when every maze has contributed its
+    episodes (each maze its first ``episodes_per_env``) -- at the latest after ``episodes_per_env * max_timestep``
+    steps, where an episode is cut off.  Under DP the totals are those of all ranks' mazes (reduce_words).
+
+    ``par``: also rate every counted solved episode against the par time of its maze, the length of the
+    shortest possible solving episode (VecMaze.par; mm_par_accum after mm_eval_accum, then mm_env_par for the
+    mazes that finished and hold their next maze); the result gains result_from_par_words' keys.  Off (the
+    default), nothing is launched and nothing is added.
+
+    ``episode_log``: also write one record per counted episode on the device (EpisodeLog: which maze, the outcome
+    and par, when the key was found and by whom, when each agent learnt the exit, when the team became exit-ready,
+    the cells covered, marks and stays).  The finished mazes' state is gone once they are reset, so the step
+    becomes: the env step with its finished mazes only queued (auto_reset=2), mm_eval_accum, mm_par_accum,
+    mm_elog_step, the queued resets, mm_elog_start and mm_env_par for the mazes that finished -- the same mazes,
+    actions and totals as without it.  The result gains ``episode_log``, this rank's records as a numpy structured
+    array (EpisodeLog.records() plus ``seed``, the maze's seed; PAR is -1 without ``par``), and ``behaviour``,
+    behaviour_from_sums' statistics over all ranks' records.  Off (the default), the step is the one above,
+    nothing is launched and nothing is added.
+
+    Returns result_from_words' dict plus ``env_steps`` and ``seconds``; with ``record`` also a dict of the
+    per-step ``actions`` [T, n, 2, 2], ``done`` [T, n] and ``reward`` [T, n] of this rank (for small n).
+    Training does not notice the call: it uses an environment and buffers of its own and leaves the rollout's
+    environment, buffers, sampler offset, the range-guard state and every random generator as they are."""
+    n, E = int(n_envs if n_envs is not None else agent.n_envs), int(episodes_per_env)
+    if n < 1 or E < 1:
+        raise ValueError("evaluate needs n_envs >= 1 and episodes_per_env >= 1")
+    kw = dict(env_config) if env_config is not None else agent._env_kwargs()
+    kw.pop("seed_base", None)
+    dev, dp, actor = agent.device, agent.dp, agent.actor
+    seeds = np.arange(n, dtype=np.uint64) + np.uint64(int(seed_base) + dp.rank * n)
+    args = (agent, n, E, seeds, kw, "greedy" if greedy else "sample", int(eval_seed) + 7919 * dp.rank,
+            max(1, int(poll)), bool(record), bool(par), bool(episode_log))
+
+    # The fp16-plane GEMMs (x2, f16) raise the library's range flag, which belongs to the rollout and the
+    # update (PPO._range_guarded).  It is only looked at here, never cleared while it carries their state: raised
+    # already -> this run uses x3 (which leaves it alone); raised BY this run -> back to clear, its state
+    # before, and the run is repeated at x3, as the update does.  Under DP both decisions are taken from the
+    # MAX over ranks (PPO._range_flags' rule): every rank runs at the same precision and issues the same
+    # collectives
+    def flag_anywhere():
+        mine = x3.range_flag(clear=False)
+        return bool(int(mine)), bool(int(dp.allreduce_max(mine.clone())))
+
+    guarded = agent.flat is not None and actor.gemm_prec != "x3"
+    prec = actor.gemm_prec
+    try:
+        if guarded and flag_anywhere()[1]:
+            actor.gemm_prec = "x3"
+            guarded = False
+        run = _run(*args)
+        if guarded:
+            mine, anywhere = flag_anywhere()
+            if anywhere:
+                if mine:  # raised by this run (it was clear before): clear again
+                    x3.range_flag(clear=True)
+                warnings.warn(f"marlmaze: a {prec} GEMM operand of the evaluation reached |x| >= 2^15 (fp16 "
+                              "planes): the evaluation is repeated at x3")
+                actor.gemm_prec = "x3"
+                run = _run(*args)
+        seconds = time.perf_counter() - run.t0
+    finally:
+        actor.gemm_prec = prec
+    words, pwords = reduce_words(run.words, run.pwords, dp, dev)
+    res = result_from_words(words)
+    if pwords is not None:
+        res.update(result_from_par_words(pwords))
+    if run.records is not None:  # this rank's records; the statistics from one summed vector of all ranks' integers
+        sums = behaviour_sums(run.records)
+        if dp.active:
+            sums = dp.allreduce_sum(torch.tensor([sums[k] for k in BEHAVIOUR_SUMS], dtype=torch.int64,
+                                                 device=dev)).tolist()
+        res["episode_log"] = run.records
+        res["behaviour"] = behaviour_from_sums(sums)
+    res["env_steps"] = n * run.steps * dp.world
+    res["seconds"] = seconds
+    return (res, run.record) if record else res
 
 
 def format_result(r):

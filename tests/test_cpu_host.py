@@ -235,6 +235,112 @@ def test_range_guard_flags_are_collective(tmp_path, world):
         assert f"FLAGS {r} {want}" in o, o
 
 
+_WORDS_WORKER = r"""
+import json, os, sys
+sys.path.insert(0, {pkg!r})
+import torch
+import torch.distributed as dist
+from marlmaze import _lib
+from marlmaze.dist import DP
+from marlmaze.evaluate import NONE_MIN, reduce_words
+rank = int(sys.argv[1])
+os.environ.update(RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=sys.argv[2])
+
+
+class CountingDP(DP):  # the collectives that reduce_words issues
+    calls = 0
+
+    def allreduce_sum(self, t):
+        self.calls += 1
+        return super().allreduce_sum(t)
+
+    def allreduce_max(self, t):
+        self.calls += 1
+        return super().allreduce_max(t)
+
+
+base = DP.from_env(backend="gloo")
+dp = CountingDP(base.rank, base.world)
+
+
+def ev(episodes, solved, sum_len, sum_len_solved, mn, mx, hist):
+    w = [0] * _lib.EVAL_WORDS
+    w[_lib.EV_EPISODES], w[_lib.EV_SOLVED], w[_lib.EV_TIMEOUTS] = episodes, solved, episodes - solved
+    w[_lib.EV_SUM_LEN], w[_lib.EV_SUM_LEN_SOLVED] = sum_len, sum_len_solved
+    w[_lib.EV_MIN_LEN_SOLVED], w[_lib.EV_MAX_LEN_SOLVED] = mn, mx
+    for b, c in hist.items():
+        w[_lib.EV_HIST0 + b] = c
+    return w
+
+
+def pw(rated, excess, hist):
+    w = [0] * _lib.PAR_WORDS
+    w[_lib.PAR_EPISODES], w[_lib.PAR_SUM_LEN], w[_lib.PAR_MAX_EXCESS] = rated, 10 * rated + rank, excess
+    for b, c in hist.items():
+        w[_lib.PAR_HIST0 + b] = c
+    return w
+
+
+nothing = ev(2, 0, 40, 0, NONE_MIN, 0, {{}})  # two timed-out episodes: the min word as mm_eval_init left it
+some = ev(3, 2, 36, 16, 7, 9, {{0: 1, 15: 1}})
+out = []
+for mine, par in (((nothing, some)[rank], None),                                   # 1, 4: one rank has nothing
+                  (nothing, None),                                                 # 2: neither has
+                  (some, pw(2 + rank, (3, 11)[rank], {{rank: 1, 5: 1 + rank}}))):      # 3: with par
+    before = dp.calls
+    w, p = reduce_words(list(mine), None if par is None else list(par), dp, torch.device("cpu"))
+    out.append(dict(words=w, pwords=p, calls=dp.calls - before))
+single = reduce_words(some, None, DP.single(), torch.device("cpu"))
+out.append(dict(same=single[0] is some and single[1] is None))
+print("WORDS", rank, json.dumps(out), flush=True)
+dist.destroy_process_group()
+"""
+
+
+def test_evaluation_words_reduce_across_ranks(tmp_path):
+    """marlmaze.evaluate.reduce_words on two gloo ranks: the sums add, the max word is the larger one and the min
+    word the smaller one, where a rank that solved nothing (min word NONE_MIN, max word 0) leaves the other rank's
+    extremes alone and two such ranks give NONE_MIN again; without par words no par collective is issued; under
+    DP.single() the input comes back as it is."""
+    import json
+
+    from marlmaze.evaluate import NONE_MIN, result_from_par_words, result_from_words
+
+    script = str(tmp_path / "words.py")
+    open(script, "w").write(_WORDS_WORKER.format(pkg=os.path.join(REPO, "marl-maze_amd")))
+    port = str(_free_port())
+    procs = [subprocess.Popen([sys.executable, script, str(r), port], stdout=subprocess.PIPE, text=True)
+             for r in range(2)]
+    outs = [p.communicate(timeout=120)[0] for p in procs]
+    assert [p.returncode for p in procs] == [0, 0]
+    got = [json.loads(re.search(rf"^WORDS {r} (.*)$", o, re.M).group(1)) for r, o in enumerate(outs)]
+    assert got[0] == got[1]  # every rank reads the same words
+    one, neither, with_par, single = got[0]
+    # 1: rank 0 solved nothing, rank 1 has min 7 and max 9
+    w = one["words"]
+    assert (w[_lib.EV_MIN_LEN_SOLVED], w[_lib.EV_MAX_LEN_SOLVED]) == (7, 9)
+    assert (w[_lib.EV_EPISODES], w[_lib.EV_SOLVED], w[_lib.EV_TIMEOUTS]) == (5, 2, 3)
+    assert (w[_lib.EV_SUM_LEN], w[_lib.EV_SUM_LEN_SOLVED]) == (76, 16)
+    assert w[_lib.EV_HIST0:] == [1] + [0] * 14 + [1] and len(w) == _lib.EVAL_WORDS
+    r = result_from_words(w)
+    assert (r["min_len_solved"], r["max_len_solved"], r["episodes"]) == (7, 9, 5)
+    # 4: no par words, no par collective: the two of the totals and nothing else (and nobody waited for more)
+    assert one["pwords"] is None and one["calls"] == 2
+    # 2: neither rank solved anything
+    w = neither["words"]
+    assert w[_lib.EV_MIN_LEN_SOLVED] == NONE_MIN and w[_lib.EV_MAX_LEN_SOLVED] == 0 and w[_lib.EV_EPISODES] == 4
+    assert result_from_words(w)["min_len_solved"] is None and neither["calls"] == 2
+    # 3: both solved (min 7 = 7, max 9 = 9, sums doubled); par's max word 3 and 11, its bins added
+    w, p = with_par["words"], with_par["pwords"]
+    assert (w[_lib.EV_MIN_LEN_SOLVED], w[_lib.EV_MAX_LEN_SOLVED], w[_lib.EV_EPISODES]) == (7, 9, 6)
+    assert p[_lib.PAR_MAX_EXCESS] == 11 and p[_lib.PAR_EPISODES] == 5 and p[_lib.PAR_SUM_LEN] == 20 + 31
+    hist = p[_lib.PAR_HIST0:]
+    assert (hist[0], hist[1], hist[5]) == (1, 1, 3) and sum(hist) == 5 and len(p) == _lib.PAR_WORDS
+    assert result_from_par_words(p)["max_excess"] == 11 and with_par["calls"] == 4
+    # 5: DP.single()
+    assert single == dict(same=True)
+
+
 @pytest.mark.parametrize("world", [2])
 def test_global_advantage_statistics(world):
     from marlmaze.dist import DP
