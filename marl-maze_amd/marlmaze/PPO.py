@@ -7,10 +7,12 @@ get_GAEs, get_rtgs, decay_lr, save/load_parameters), same checkpoint dict
 move both ways.  What changes is where the work runs:
 
 * rollout: ``n_envs`` mazes step together in HBM (VecMaze, HIP kernels); per
-  step one critic call on all [N, 130] observations, one actor call on all
-  [2N, 65] agent rows, one sampler kernel (masked Categorical + Bernoulli,
-  PPO.py:170-186) and one env-step kernel.  No host synchronisation inside
-  the rollout.
+  step one actor call on all [2N, 65] agent rows, one sampler kernel (masked
+  Categorical + Bernoulli, PPO.py:170-186) and one env-step kernel, then one
+  critic call on every step's [N, 130] observations.  No host synchronisation
+  inside the rollout.  The buffers, the step and the collectors (fixed horizon, its
+  captured replay, whole episodes) live in marlmaze.rollout; ``rollout``,
+  ``get_batch``, ``_ensure_env`` and ``_carry_over`` here are calls of them.
 * GAE: one HIP scan over the time-major [T, N] buffers (PPO.get_GAEs,
   PPO.py:193-203, bit-exact fp32).
 * update: the clipped-surrogate + value-MSE minibatch loop of PPO.py:46-85,
@@ -33,19 +35,11 @@ import warnings
 import numpy as np
 import torch
 
-from . import networks, ops, update, x3
+from . import _lib, networks, ops, rollout, update, x3
 from .dist import DP
 from .networks import Actor, Critic
-from .vecmaze import VecMaze
 
 MODEL_PATH = "PPO.pth"  # PPO.py:9 (CWD-relative)
-# the captured rollout's critic on a side stream (a parallel branch of the graph): MARLMAZE_ROLLOUT_SIDE=0 keeps
-# it on the main stream (A/B)
-ROLLOUT_SIDE_STREAM = os.environ.get("MARLMAZE_ROLLOUT_SIDE", "1") != "0"
-# the rollout's critic values in ONE launch over all T (+1) steps' observations after the env loop (they depend on
-# the observations only, and the weights do not change during a rollout): no critic launch and no cross-stream
-# hand-off per step.  MARLMAZE_ROLLOUT_CRITIC=step keeps the per-step form (A/B)
-ROLLOUT_BATCHED_CRITIC = os.environ.get("MARLMAZE_ROLLOUT_CRITIC", "batched") != "step"
 # the update's critic (forward, value loss, backward) on a side stream beside the actor's kernels: the two
 # networks share nothing until the loss values and the optimizer step.  At small minibatches (BASELINE
 # configs[1]: 26,214 samples) the kernels of either network leave most CUs idle, and at the headline's 209,715
@@ -58,8 +52,6 @@ CRITIC_STREAM_MAX_SAMPLES = int(os.environ.get("MARLMAZE_CRITIC_STREAM_MAX", "65
 
 def _ppo_loss_fwd(heads, mk, a8, old_logp, adv, clip):
     """mm_ppo_loss: (coef [M] = d loss / d logp, per-workgroup partial sums of the surrogate)."""
-    from . import _lib
-
     L = _lib.lib()
     M = old_logp.shape[0]
     old_logp, adv = old_logp.contiguous(), adv.contiguous()
@@ -72,8 +64,6 @@ def _ppo_loss_fwd(heads, mk, a8, old_logp, adv, clip):
 
 def _ppo_loss_bwd(heads, mk, a8, coef, dloss):
     """mm_ppo_loss_bwd: d loss / d heads [2M, 6] (dloss: a 1-element device tensor)."""
-    from . import _lib
-
     dz = torch.empty_like(heads)
     _lib.check(_lib.lib().mm_ppo_loss_bwd(_lib.ptr(heads), _lib.ptr(mk), _lib.ptr(a8), _lib.ptr(coef),
                                           _lib.ptr(dloss), coef.shape[0], _lib.ptr(dz), _lib.stream_ptr()),
@@ -173,7 +163,7 @@ class PPO:
         self.horizon = int(horizon) if horizon else max(1, math.ceil(batch_size / (self.n_envs * self.dp.world)))
         self.env_config = env_config
         self.bootstrap = bootstrap
-        self.episode_batches = bool(episode_batches)  # the reference's whole-episode batches (_episode_batch)
+        self.episode_batches = bool(episode_batches)  # the reference's whole-episode batches (rollout.episode_batch)
         self.episode_chunk = int(episode_chunk)
         self._fresh = False  # the env was just reset (its first batch needs no reset of its own)
         self.sample_seed = (sample_seed if sample_seed is not None else random.getrandbits(63)) + 7919 * self.dp.rank
@@ -186,20 +176,15 @@ class PPO:
         self._bufs = None
         self.history = []
         self.step_events = None  # list -> rollout records (start, end) events around each env step
-        # capture the fixed-horizon rollout (every step's critic, actor trunk, head + sampler, env step and
-        # the GAE) in one HIP graph and replay it: at a few thousand mazes the ~15 launches per step are
-        # host-bound, a replay is one launch
+        # capture the fixed-horizon rollout (every step's actor trunk, head + sampler and env step, the critic
+        # and the GAE) in one HIP graph and replay it (rollout.captured)
         self.graph_rollout = bool(graph_rollout)
-        self._graph = None
+        self._replay = rollout.Replay()
         self.range_redos = 0  # updates redone at x3 by the range guard (_range_guarded)
         self.range_switched = False  # the rollout's operands left the fp16 range: the networks now run x3
         self.batches_discarded = 0  # batches the range guard threw away (their rollout left the fp16 range)
         self.last_update_discarded = False
         self._flag_armed = False  # a rollout cleared the range flag at its start: the next update reads its flag
-        self._graph_key = None
-        self._graph_warm = False
-        self._ctr = None  # device base of the sampler's Philox offset in graph replays
-        self._ctr_val = None
         if load:
             self.load_parameters()
 
@@ -216,34 +201,10 @@ class PPO:
                     rand_start=m.rand_start, rand_sizes=m.rand_sizes, rand_range=tuple(m.rand_range))
 
     def _ensure_env(self):
-        if self.venv is not None:
-            return
-        n = self.n_envs
-        base = int(self.env_config.get("seed_base", 0)) if self.env_config else random.getrandbits(32)
-        kw = {k: v for k, v in self._env_kwargs().items() if k != "seed_base"}
-        seeds = np.arange(n, dtype=np.uint64) + np.uint64(base) + np.uint64(self.dp.rank * n)
-        self.venv = VecMaze(n, seeds=seeds, device=self.device, **kw)
-        T, d = self.horizon, self.device
-        self._bufs = dict(
-            obs=torch.zeros((T + 1, n, 2, 65), dtype=torch.float32, device=d),
-            masks=torch.zeros((T + 1, n, 2, 6), dtype=torch.uint8, device=d),
-            act=torch.zeros((T, n, 2, 2), dtype=torch.int8, device=d),
-            logp=torch.zeros((T, n), dtype=torch.float32, device=d),
-            rowlogp=torch.zeros((T, 2 * n), dtype=torch.float32, device=d),
-            val_all=torch.zeros((T + 1, n), dtype=torch.float32, device=d),  # [T] values + the bootstrap row
-            rew=torch.zeros((T, n), dtype=torch.float32, device=d),
-            done=torch.zeros((T, n), dtype=torch.uint8, device=d),
-            stats=torch.zeros((T, n, 2), dtype=torch.int32, device=d),
-            adv=torch.zeros((T, n), dtype=torch.float32, device=d),
-            rtg=torch.zeros((T, n), dtype=torch.float32, device=d),
-        )
-        self._bufs["val"] = self._bufs["val_all"][:T]
-        self._bufs["last_val"] = self._bufs["val_all"][T]
-        self.venv.reset(obs=self._bufs["obs"][0], masks=self._bufs["masks"][0])
-        self._fresh = True
+        rollout.ensure_env(self)
 
     # ------------------------------------------------------------------
-    # rollout (PPO.get_batch, PPO.py:89-152)
+    # rollout (PPO.get_batch, PPO.py:89-152): marlmaze.rollout
     # ------------------------------------------------------------------
     def _arm_range_flag(self):
         """A rollout starts: clear the library's range flag, so that what the next update reads as the
@@ -254,254 +215,26 @@ class PPO:
 
     @torch.no_grad()
     def rollout(self):
-        """Advance every maze ``horizon`` steps; fills the [T, N] buffers."""
+        """Advance every maze ``horizon`` steps; fills and returns the [T, N] buffers (``_bufs``).  With
+        ``graph_rollout`` (and no ``step_events`` instrumentation): a replay of the captured rollout."""
         self._arm_range_flag()
         self._ensure_env()
-        b, n, T = self._bufs, self.n_envs, self.horizon
-        if self.graph_rollout and self.step_events is None and self.device.type == "cuda":
-            return self._rollout_graph(b, n, T)
-        with x3.cached_packs():  # the weights are fixed during the rollout: pack them once, not per step
-            return self._rollout_steps_deferred(b, n, T)
+        if self.graph_rollout and self.step_events is None:
+            return rollout.captured(self)
+        return rollout.fixed_horizon(self)
 
-    def _rollout_steps_deferred(self, b, n, T):
-        """_rollout_steps with the side-stream maze pre-generation queued once, after the last step
-        (VecMaze.defer_pregen): the steps' kernels get the GPU to themselves."""
-        self.venv.defer_pregen = True
-        try:
-            return self._rollout_steps(b, n, T)
-        finally:
-            self.venv.defer_pregen = False
-            self.venv.flush_pregen()
-
-    def _rollout_graph(self, b, n, T):
-        """The rollout as a replay of a captured HIP graph (same kernels, same
-        draws: the sampler reads its Philox base offset from the device)."""
-        # everything the captured launches hold by value: a change re-captures
-        key = (id(self.venv), self.flat.data.data_ptr() if self.flat is not None else None, T, id(b["obs"]),
-               self.sample_seed, float(self.discount_rate), float(self.lam), bool(self.bootstrap))
-        if self._graph is None or self._graph_key != key:
-            if not self._graph_warm:  # the first rollout runs uncaptured (one-time host work: kernel attributes)
-                self._graph_warm = True
-                with x3.cached_packs():
-                    return self._rollout_steps_deferred(b, n, T)
-            self._graph = torch.cuda.CUDAGraph()
-            self._ctr = torch.tensor([self._sample_offset], dtype=torch.int64, device=self.device)
-            self._ctr_val = self._sample_offset
-            torch.cuda.synchronize(self.device)
-            self.venv.capturing = True
-            try:
-                with torch.cuda.graph(self._graph):
-                    with x3.cached_packs():
-                        self._rollout_steps(b, n, T, offset_dev=self._ctr)
-                    self._ctr += T
-            finally:
-                self.venv.capturing = False
-            self._graph_key = key
-        if self._ctr_val != self._sample_offset:  # an uncaptured rollout ran in between
-            self._ctr.fill_(self._sample_offset)
-        self._graph.replay()
-        self._sample_offset += T
-        self._ctr_val = self._sample_offset
-        self.venv._kick_pregen()  # refill the next mazes the replay's resets consumed
-        return b
-
-    def _rollout_steps(self, b, n, T, offset_dev=None):
-        head_w, head_b = self.actor.heads()
-        cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        # the critic reads only the observations, which stay in the [T + 1] buffer: by default its values for
-        # every step come from one launch after the loop (ROLLOUT_BATCHED_CRITIC); the per-step form runs it on
-        # a side stream beside the actor when the rollout is captured (two branches of the graph)
-        batched = ROLLOUT_BATCHED_CRITIC and cur is not None
-        side = (self._critic_stream() if (self.graph_rollout and cur is not None and ROLLOUT_SIDE_STREAM
-                                          and not batched) else None)
-        for t in range(T):
-            obs_t = b["obs"][t]
-            if batched:
-                pass
-            elif side is not None:
-                side.wait_stream(cur)  # obs[t] written by the previous step's env kernel
-                with torch.cuda.stream(side):
-                    self.critic.value_into(obs_t, b["val"][t])
-            elif cur is not None:
-                self.critic.value_into(obs_t, b["val"][t])
-            else:
-                b["val"][t] = self.critic(obs_t).view(n)
-            # actor trunk, heads and sampling (PPO.py:170-186): one launch after the front-end at small N
-            # (Actor.sample_actions), else the trunk's GEMMs + ops.head_act (Actor.act)
-            self.actor.sample_actions(obs_t.view(2 * n, 65), head_w, head_b, b["masks"][t].view(2 * n, 6),
-                                      self.sample_seed, t if offset_dev is not None else self._sample_offset,
-                                      actions=b["act"][t].view(2 * n, 2), logp=b["rowlogp"][t],
-                                      joint_logp=b["logp"][t], offset_dev=offset_dev)
-            if offset_dev is None:
-                self._sample_offset += 1
-            ev = self.step_events
-            if ev is None:
-                self.venv.step(b["act"][t], auto_reset=True, obs=b["obs"][t + 1], masks=b["masks"][t + 1],
-                               reward=b["rew"][t], done=b["done"][t], ep_stats=b["stats"][t])
-            else:  # instrumented: HIP events stamped at the env-step kernel's own start / end
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()  # materialise the events; the launch re-stamps them
-                e1.record()
-                self.venv.step(b["act"][t], auto_reset=2, obs=b["obs"][t + 1], masks=b["masks"][t + 1],
-                               reward=b["rew"][t], done=b["done"][t], ep_stats=b["stats"][t], events=(e0, e1))
-                self.venv.reset_done(obs=b["obs"][t + 1], masks=b["masks"][t + 1])
-                ev.append((e0, e1))
-        if side is not None:
-            cur.wait_stream(side)  # every value written before the GAE reads them
-        last = None
-        if batched:  # V(s_0 .. s_T-1) (and V(s_T) for the bootstrap) in one launch
-            rows = T + 1 if self.bootstrap else T
-            self.critic.value_into(b["obs"][:rows].reshape(rows * n, -1), b["val_all"][:rows].reshape(rows * n))
-            last = b["last_val"] if self.bootstrap else None
-        elif self.bootstrap:  # (the per-step values' arithmetic for V(s_T) too)
-            if cur is not None:
-                self.critic.value_into(b["obs"][T], b["last_val"])
-            else:
-                b["last_val"].copy_(self.critic(b["obs"][T]).view(n))
-            last = b["last_val"]
-        ops.gae(b["rew"], b["val"], b["done"], last_value=last, gamma=self.discount_rate, lam=self.lam,
-                adv=b["adv"], rtg=b["rtg"])
-        return b
-
-    def _critic_stream(self):
-        if getattr(self, "_cstream", None) is None:
-            self._cstream = torch.cuda.Stream(device=self.device)
-        return self._cstream
+    @property
+    def _graph(self):
+        return self._replay.graph
 
     def _carry_over(self):
-        """The next batch starts from the last observation (episodes continue)."""
-        b = self._bufs
-        b["obs"][0].copy_(b["obs"][self.horizon])
-        b["masks"][0].copy_(b["masks"][self.horizon])
-
-    @torch.no_grad()
-    def _episode_batch(self):
-        """PPO.get_batch (PPO.py:89-152) over ``n_envs`` mazes, whole episodes only.
-
-        Every maze is reset (PPO.py:104) and all step together.  The batch ends
-        at the first step t* after which the steps of completed episodes (all
-        mazes) exceed ``batch_size`` (per rank under DP) -- with one maze that is
-        the reference's rule, the first episode end after more than
-        ``batch_size`` steps (PPO.py:126-141).  Episodes still running at t* are
-        dropped (the reference keeps only complete episodes).  Samples are
-        ordered maze by maze, each maze's episodes in time order (one maze: the
-        reference's order), and GAE runs on whole episodes (PPO.py:133; the
-        episode-parallel walk of mm_gae_ex, bit-exact).  No step past t* may
-        leave a trace (a maze finishing there would draw its next maze from its
-        RNG stream, which the reference never does): after step t at most n (t + 1) steps
-        can belong to completed episodes, so the steps before
-        t_min = batch_size // n run in chunks of ``episode_chunk`` with one host
-        synchronisation per chunk.  From t_min on the chunks grow geometrically
-        (1, 2, 4, ... up to ``episode_chunk`` steps) from an environment
-        snapshot: when the stop step falls inside a chunk, the environment is
-        rewound to the chunk's start and only the steps up to t* are replayed
-        with the recorded actions, so neither the MT19937 streams nor the
-        sampler's Philox offset carry any trace of the overshoot into the next
-        batch.
-        """
-        self._arm_range_flag()
-        self._ensure_env()
-        n, dev = self.n_envs, self.device
-        limit = self.batch_size // self.dp.world
-        if self._fresh:  # the state at the batch's first step
-            obs0, masks0 = self._bufs["obs"][0].clone(), self._bufs["masks"][0].clone()
-        else:
-            obs0 = torch.empty((n, 2, 65), dtype=torch.float32, device=dev)
-            masks0 = torch.empty((n, 2, 6), dtype=torch.uint8, device=dev)
-            self.venv.reset(obs=obs0, masks=masks0)  # PPO.py:104
-        self._fresh = False
-        head_w, head_b = self.actor.heads()
-        chunks = []
-        last_end = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        t0, t_stop, end_at_stop = 0, None, None
-        t_min = limit // n  # the first step after which the batch can be full
-        tail = 1  # the next chunk length past t_min
-        self._episode_replayed = 0
-        with x3.cached_packs():  # the weights are fixed during the batch: packed once, not per step
-            while t_stop is None:
-                if t0 < t_min:
-                    C, snap = min(self.episode_chunk, t_min - t0), None
-                else:
-                    C, tail = tail, min(2 * tail, self.episode_chunk)
-                    snap, off0 = self.venv.snapshot(), self._sample_offset
-                ch = dict(obs=torch.empty((C + 1, n, 2, 65), dtype=torch.float32, device=dev),
-                          masks=torch.empty((C + 1, n, 2, 6), dtype=torch.uint8, device=dev),
-                          act=torch.empty((C, n, 2, 2), dtype=torch.int8, device=dev),
-                          logp=torch.empty((C, n), dtype=torch.float32, device=dev),
-                          rowlogp=torch.empty((C, 2 * n), dtype=torch.float32, device=dev),
-                          val=torch.empty((C, n), dtype=torch.float32, device=dev),
-                          rew=torch.empty((C, n), dtype=torch.float32, device=dev),
-                          done=torch.empty((C, n), dtype=torch.uint8, device=dev),
-                          stats=torch.empty((C, n, 2), dtype=torch.int32, device=dev))
-                ch["obs"][0].copy_(obs0)
-                ch["masks"][0].copy_(masks0)
-                for t in range(C):
-                    # the fixed-horizon rollout's value arithmetic (value_into: the fused fp32 kernel), so a
-                    # network's stored values do not depend on the batch mode
-                    self.critic.value_into(ch["obs"][t], ch["val"][t])
-                    self.actor.sample_actions(ch["obs"][t].view(2 * n, 65), head_w, head_b,
-                                              ch["masks"][t].view(2 * n, 6), self.sample_seed, self._sample_offset,
-                                              actions=ch["act"][t].view(2 * n, 2), logp=ch["rowlogp"][t],
-                                              joint_logp=ch["logp"][t])
-                    self._sample_offset += 1
-                    self.venv.step(ch["act"][t], auto_reset=True, obs=ch["obs"][t + 1], masks=ch["masks"][t + 1],
-                                   reward=ch["rew"][t], done=ch["done"][t], ep_stats=ch["stats"][t])
-                chunks.append(ch)
-                obs0, masks0 = ch["obs"][C], ch["masks"][C]
-                # completed-episode steps after each step of the chunk: sum over mazes of (last end + 1)
-                tt = torch.arange(t0, t0 + C, device=dev).view(C, 1)
-                ends = torch.where(ch["done"].bool(), tt, torch.full_like(tt, -1))
-                ends = torch.maximum(torch.cummax(ends, 0).values, last_end.view(1, n))
-                filled = (ends + 1).sum(1)
-                hit = torch.nonzero(filled > limit)
-                if hit.numel():  # one host synchronisation per chunk; only a tail chunk can hit
-                    k = int(hit[0, 0])
-                    t_stop, end_at_stop = t0 + k, ends[k]
-                    if k + 1 < C:  # overshoot: rewind to the chunk's start, replay steps t0 .. t* only
-                        self.venv.restore(snap)
-                        for t in range(k + 1):
-                            self.venv.step(ch["act"][t], auto_reset=True, obs=ch["obs"][t + 1],
-                                           masks=ch["masks"][t + 1], reward=ch["rew"][t], done=ch["done"][t],
-                                           ep_stats=ch["stats"][t])
-                        self._sample_offset = off0 + k + 1
-                        self._episode_replayed = k + 1
-                else:
-                    last_end = ends[-1]
-                    t0 += C
-        Ts = t_stop + 1  # == the steps kept (the last chunk may hold discarded steps past t_stop)
-        cat = {k: torch.cat([c[k][:c["act"].shape[0]] for c in chunks], 0)[:Ts]
-               for k in ("obs", "masks", "act", "logp", "val", "rew", "done", "stats")}
-        adv, rtg = ops.gae(cat["rew"], cat["val"], cat["done"], gamma=self.discount_rate, lam=self.lam)
-        keep = torch.arange(Ts, device=dev).view(Ts, 1) <= end_at_stop.view(1, n)
-        nt = torch.nonzero(keep.t())  # (maze, t), maze-major, t ascending
-        flat = nt[:, 1] * n + nt[:, 0]
-        B = flat.numel()
-        pick = lambda x, *shape: x.reshape(Ts * n, *shape)[flat]  # noqa: E731
-        st = pick(cat["stats"], 2)
-        fin = st[:, 0] > 0
-        out = (pick(cat["obs"], 2, 65), pick(cat["act"], 2, 2).float(), pick(cat["logp"]),
-               st[fin, 1].tolist(), st[fin, 0].tolist(), pick(cat["masks"], 2, 6).bool(), pick(adv), pick(cat["val"]))
-        self._episode_info = dict(t_stop=t_stop, samples=B, rtg=pick(rtg), act=cat["act"], done=cat["done"])
-        return out
+        rollout.carry_over(self)
 
     def get_batch(self):
         """Reference 8-tuple (PPO.py:151-152).  Default: every maze advances
         ``horizon`` steps, samples flattened time-major.  ``episode_batches``:
-        whole episodes only (_episode_batch)."""
-        if self.episode_batches:
-            return self._episode_batch()
-        b = self.rollout()
-        T, n = self.horizon, self.n_envs
-        B = T * n
-        out = (b["obs"][:T].reshape(B, 2, 65).clone(), b["act"].reshape(B, 2, 2).float(),
-               b["logp"].reshape(B).clone(), None, None, b["masks"][:T].reshape(B, 2, 6).bool(),
-               b["adv"].reshape(B).clone(), b["val"].reshape(B).clone())
-        st = b["stats"].reshape(B, 2)
-        fin = st[:, 0] > 0
-        ep_lens = st[fin, 0].tolist()
-        shortest = st[fin, 1].tolist()
-        self._carry_over()
-        return out[:3] + (shortest, ep_lens) + out[5:]
+        whole episodes only (rollout.episode_batch)."""
+        return rollout.episode_batch(self) if self.episode_batches else rollout.horizon_batch(self)
 
     # ------------------------------------------------------------------
     # update (PPO.py:46-85)
@@ -537,35 +270,15 @@ class PPO:
         mk = _u8(masks)
         if out is None:
             out = torch.empty(2, dtype=torch.float32, device=obs.device)
-        side = CRITIC_STREAM == "on" or (CRITIC_STREAM == "auto" and M <= CRITIC_STREAM_MAX_SAMPLES)
-        if side:
-            return self._minibatch_grads_two_streams(obs, a8, old_logp, adv, rtg, mk, out)
+        # the critic beside the actor (CRITIC_STREAM): its launches go to the device's "critic" side stream, which
+        # waits for the weight packs; this stream waits for it before the loss values and the optimizer.  Off:
+        # the same launches on this stream, in the order written (the same results bit for bit)
+        beside = CRITIC_STREAM == "on" or (CRITIC_STREAM == "auto" and M <= CRITIC_STREAM_MAX_SAMPLES)
         with x3.cached_packs():
-            # every weight pack of both networks' forward and backward in one launch per precision, and
-            # the backwards' bias-gradient and weight-gradient reductions together at their end
+            # every weight pack of both networks' forward and backward in one launch per precision, and each
+            # backward's bias-gradient and weight-gradient reductions together at its end
             x3.pack_many(self.critic.pack_specs() + self.actor.pack_specs())
-            V, csaved = self.critic.train_forward(obs.reshape(M, -1))
-            mse_part, dv = update.mse_loss(V, rtg)
-            heads, asaved = self.actor.train_forward(obs.reshape(2 * M, 65))
-            coef, ppo_part = _ppo_loss_fwd(heads, mk, a8, old_logp, adv, self.clip)
-            dz = _ppo_loss_bwd(heads, mk, a8, coef, self._one)
-            update.losses_final(ppo_part, mse_part, M, out)
-            with x3.deferred():
-                self.actor.train_backward(asaved, dz)
-                self.critic.train_backward(csaved, dv)
-        return out[0], out[1]
-
-    def _minibatch_grads_two_streams(self, obs, a8, old_logp, adv, rtg, mk, out):
-        """minibatch_grads with the critic's forward, value loss and backward on a side stream, beside the
-        actor's (the same kernels and arithmetic: the same results bit for bit).  The side stream waits for
-        the weight packs; the main stream waits for the critic before the loss values and the optimizer."""
-        M = obs.shape[0]
-        cur = torch.cuda.current_stream(obs.device)
-        side = self._critic_update_stream()
-        with x3.cached_packs():
-            x3.pack_many(self.critic.pack_specs() + self.actor.pack_specs())
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+            with _lib.on_side(_lib.side_stream("critic", obs.device) if beside else None) as critic_side:
                 V, csaved = self.critic.train_forward(obs.reshape(M, -1))
                 mse_part, dv = update.mse_loss(V, rtg)
                 with x3.deferred():
@@ -575,15 +288,9 @@ class PPO:
             dz = _ppo_loss_bwd(heads, mk, a8, coef, self._one)
             with x3.deferred():
                 self.actor.train_backward(asaved, dz)
-            cur.wait_stream(side)
-            mse_part.record_stream(cur)  # (allocated on the side stream, read on this one)
+            critic_side.join(mse_part)
             update.losses_final(ppo_part, mse_part, M, out)
         return out[0], out[1]
-
-    def _critic_update_stream(self):
-        if getattr(self, "_cupd_stream", None) is None:
-            self._cupd_stream = torch.cuda.Stream(device=self.device)
-        return self._cupd_stream
 
     def _minibatch_grads_host(self, obs, act, old_logp, adv, rtg, masks):
         """The CPU torch form (autograd, the reference's formulas)."""
@@ -692,15 +399,9 @@ class PPO:
         """The precision of both networks' GEMMs on the GPU ("x2", "x3" or "f16")."""
         assert prec in networks.GEMM_PRECISIONS
         self.gemm_prec = self.actor.gemm_prec = self.critic.gemm_prec = prec
-        self._graph = None  # a captured rollout holds the old precision's kernels
-
-    def _range_flags(self, pre, post):
-        """(pre_set, post_set) from this rank's two device flags, decided for ALL ranks: under DP the flags
-        are MAX-all-reduced before the one host read, so a range violation on any rank's shard takes every
-        rank down the same branch (the same redo, the same collectives, identical parameters after it)."""
-        flags = torch.cat([pre, post])
-        self.dp.allreduce_max(flags)
-        return tuple(int(v) for v in flags.tolist())  # the synchronisation
+        # a captured rollout holds the old precision's kernels: start over (the new precision's kernels run
+        # uncaptured once, then they are captured)
+        self._replay = rollout.Replay()
 
     def _range_guarded(self, passes):
         """Run the update passes; if any GEMM operand they converted to fp16 planes had |x s| >= 2^15 (the
@@ -710,36 +411,20 @@ class PPO:
         fp32 policy (an inf / NaN accumulator can become 0 through a ReLU): the update on it is thrown away
         (parameters and optimizer state restored, hist NaN, ``last_update_discarded``), and both networks run
         their GEMMs at x3 from now on (``train`` then collects a new batch).  One host synchronisation per
-        update (the flags' read)."""
+        update (the flags' read, DP.raised_on_any_rank: under DP every rank takes the same branch)."""
         # the flag raised since this agent's last rollout began (its actor GEMMs); a batch that did not come
         # from a rollout of this agent (update() on given tensors) has no rollout flag: a stale one is dropped
         pre = x3.range_flag(clear=True)
         if not self._flag_armed:
             pre.zero_()
         self._flag_armed = False
-        flat = self.flat
-        opts = (self.actor_optim, self.critic_optim)
-        moments = {id(t): t for o in opts for t in (o.exp_avg, o.exp_avg_sq)}
-        snap = (flat.data.clone(), {k: t.clone() for k, t in moments.items()}, [o.t for o in opts],
-                [[g["lr"] for g in o.param_groups] for o in opts])
-
-        def restore():
-            with torch.no_grad():
-                flat.data.copy_(snap[0])
-                for k, t in moments.items():
-                    t.copy_(snap[1][k])
-            for o, t, lrs in zip(opts, snap[2], snap[3]):
-                o.t = t
-                for g, lr in zip(o.param_groups, lrs):
-                    g["lr"] = lr
-            x3.invalidate_packs()
-
+        snap = update.Snapshot(self.flat, (self.actor_optim, self.critic_optim))
         hist = passes()
         post = x3.range_flag(clear=True)
-        pre_set, post_set = self._range_flags(pre, post)
+        pre_set, post_set = self.dp.raised_on_any_rank(pre, post)
         self.last_update_discarded = bool(pre_set)
         if pre_set:
-            restore()
+            snap.restore()
             warnings.warn(f"marlmaze: a {self.gemm_prec} GEMM operand of the rollout reached |x| >= 2^15 (fp16 "
                           "planes): the update on this batch is discarded, and both networks run their GEMMs at "
                           "x3 (bf16x3, fp32 range) from now on")
@@ -749,7 +434,7 @@ class PPO:
             hist.fill_(float("nan"))
             return hist
         if post_set:
-            restore()
+            snap.restore()
             prec = self.gemm_prec
             self.set_gemm_prec("x3")
             try:

@@ -317,3 +317,43 @@ def ptr(t):
 def stream_ptr(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
+
+
+_SIDE_STREAMS = {}
+
+
+def side_stream(name, device):
+    """The side stream ``name`` of a device: one per name and device, created on first use."""
+    key = (name, torch.device(device))
+    if key not in _SIDE_STREAMS:
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
+    return _SIDE_STREAMS[key]
+
+
+class on_side:
+    """with on_side(side) as s: the block's launches go to the stream ``side``, after everything queued so far on
+    the current stream.  s.join(*tensors), after the block: the current stream waits for them, and the tensors
+    (made in the block, on the side stream) are not reused by the caching allocator before this stream's work on
+    them is done.  side None: the block runs on the current stream and join does nothing."""
+
+    def __init__(self, side):
+        self.side = side
+
+    def __enter__(self):
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream(self.side.device))
+            self.ctx = torch.cuda.stream(self.side)
+            self.ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self.side is not None:
+            self.ctx.__exit__(*exc)
+        return False
+
+    def join(self, *tensors):
+        if self.side is not None:
+            cur = torch.cuda.current_stream(self.side.device)
+            cur.wait_stream(self.side)
+            for t in tensors:
+                t.record_stream(cur)

@@ -134,6 +134,13 @@ class DP:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t
 
+    def raised_on_any_rank(self, *flags):
+        """This rank's one-element device flags -> a tuple of ints, each the flag's MAX over ranks: one
+        collective, then the one host read (the synchronisation).  The range guard's rule: a range violation on
+        any rank's shard takes every rank down the same branch (the same redo, the same collectives, identical
+        parameters after it).  The flags themselves are left as they are."""
+        return tuple(int(v) for v in self.allreduce_max(torch.cat(flags)).tolist())
+
     def barrier(self):
         if self.active:
             dist.barrier()

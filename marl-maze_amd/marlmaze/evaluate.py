@@ -424,23 +424,19 @@ def evaluate_policy(agent, episodes_per_env=1, greedy=True, n_envs=None, env_con
     # update (PPO._range_guarded).  It is only looked at here, never cleared while it carries their state: raised
     # already -> this run uses x3 (which leaves it alone); raised BY this run -> back to clear, its state
     # before, and the run is repeated at x3, as the update does.  Under DP both decisions are taken from the
-    # MAX over ranks (PPO._range_flags' rule): every rank runs at the same precision and issues the same
-    # collectives
-    def flag_anywhere():
-        mine = x3.range_flag(clear=False)
-        return bool(int(mine)), bool(int(dp.allreduce_max(mine.clone())))
-
+    # MAX over ranks (DP.raised_on_any_rank, the update's rule): every rank runs at the same precision and issues
+    # the same collectives
     guarded = agent.flat is not None and actor.gemm_prec != "x3"
     prec = actor.gemm_prec
     try:
-        if guarded and flag_anywhere()[1]:
+        if guarded and dp.raised_on_any_rank(x3.range_flag(clear=False))[0]:
             actor.gemm_prec = "x3"
             guarded = False
         run = _run(*args)
         if guarded:
-            mine, anywhere = flag_anywhere()
-            if anywhere:
-                if mine:  # raised by this run (it was clear before): clear again
+            mine = x3.range_flag(clear=False)
+            if dp.raised_on_any_rank(mine)[0]:
+                if int(mine):  # raised by this run (it was clear before): clear again
                     x3.range_flag(clear=True)
                 warnings.warn(f"marlmaze: a {prec} GEMM operand of the evaluation reached |x| >= 2^15 (fp16 "
                               "planes): the evaluation is repeated at x3")

@@ -17,6 +17,8 @@ copies.  Here:
   -- with the moments in flat buffers.
 * ``clip_adam`` is clip_grad_norm_ + Adam for both networks in two launches
   (``mm_clip_adam``, csrc/update_kernels.hip).
+* ``Snapshot`` holds the parameters and the optimizers' state as they were before
+  an update, for the range guard's undo.
 """
 import math
 
@@ -160,6 +162,28 @@ class FlatAdam:
         s.bc2_sqrt = math.sqrt(1.0 - b2 ** t)
         s.grad_scale = float(grad_scale)
         return s
+
+
+class Snapshot:
+    """The state an update changes, as it is now: the flat parameter buffer, the optimizers' (shared) Adam
+    moments, each optimizer's step count and learning rates.  restore() puts it back (the range guard's undo,
+    PPO._range_guarded)."""
+
+    def __init__(self, flat, opts):
+        self.opts = opts
+        self.live = [flat.data] + list({id(t): t for o in opts for t in (o.exp_avg, o.exp_avg_sq)}.values())
+        self.saved = [t.clone() for t in self.live]
+        self.steps = [(o.t, [g["lr"] for g in o.param_groups]) for o in opts]
+
+    def restore(self):
+        with torch.no_grad():
+            for t, s in zip(self.live, self.saved):
+                t.copy_(s)
+        for o, (t, lrs) in zip(self.opts, self.steps):
+            o.t = t
+            for g, lr in zip(o.param_groups, lrs):
+                g["lr"] = lr
+        x3.invalidate_packs()  # parameters changed behind torch's version counters
 
 
 def clip_adam(opts, max_norm, norms=None, grad_scale=1.0):

@@ -199,21 +199,19 @@ def test_integration_struct_matches_header():
 
 
 _FLAG_WORKER = r"""
-import os, sys, types
+import os, sys
 sys.path.insert(0, {pkg!r})
 import torch
 import torch.distributed as dist
 from marlmaze.dist import DP
-from marlmaze.PPO import PPO
 rank, world = int(sys.argv[1]), int(sys.argv[3])
 os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=sys.argv[2])
 dp = DP.from_env(backend="gloo")
-me = types.SimpleNamespace(dp=dp)
 out = []
 for pre_rank, post_rank in ((None, world - 1), (0, None), (None, None), (1, 1)):
     pre = torch.tensor([int(rank == pre_rank)], dtype=torch.int32)
     post = torch.tensor([int(rank == post_rank)], dtype=torch.int32)
-    out.append(PPO._range_flags(me, pre, post))
+    out.append(dp.raised_on_any_rank(pre, post))
 print("FLAGS", rank, out, flush=True)
 dist.destroy_process_group()
 """
@@ -221,7 +219,7 @@ dist.destroy_process_group()
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_range_guard_flags_are_collective(tmp_path, world):
-    """PPO._range_flags (the x2 range guard's decision): a flag raised on ONE rank is seen by every rank (MAX
+    """DP.raised_on_any_rank (the x2 range guard's decision): a flag raised on ONE rank is seen by every rank (MAX
     all-reduce before the host read), so all ranks redo / discard together and issue the same collectives."""
     script = str(tmp_path / "flags.py")
     open(script, "w").write(_FLAG_WORKER.format(pkg=os.path.join(REPO, "marl-maze_amd")))

@@ -1,4 +1,4 @@
-"""The x2 range guard under data parallelism (PPO._range_guarded, PPO._range_flags): the redo / discard
+"""The x2 range guard under data parallelism (PPO._range_guarded, DP.raised_on_any_rank): the redo / discard
 decision is taken from the MAX over ranks of every rank's range flags, so a range violation on ONE rank's
 shard takes every rank down the same branch -- the same collectives, identical parameters afterwards.
 

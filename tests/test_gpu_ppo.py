@@ -550,19 +550,49 @@ def test_graph_rollout_equals_eager(n):
     assert ags[1]._graph is not None and ags[0]._sample_offset == ags[1]._sample_offset
 
 
+def test_graph_rollout_recaptured_after_set_gemm_prec():
+    """set_gemm_prec drops the captured rollout (its graph holds the old precision's kernels): after a switch
+    to x3 the captured agent still gives the eager agent's batches bit for bit, its sampler offset is the eager
+    one's, and the graph it then holds is a new one."""
+    cfg = dict(default_size=(6, 6), max_timestep=20, seed_base=7)
+    n, T = 512, 8
+    ags = [_agent(n_envs=n, horizon=T, batch_size=n * T, sample_seed=5, env_config=cfg, graph_rollout=g)
+           for g in (False, True)]
+
+    def two_rollouts(it0):
+        for it in range(it0, it0 + 2):
+            outs = []
+            for ag in ags:
+                b = ag.rollout()
+                outs.append({k: v.clone() for k, v in b.items()})
+                ag._carry_over()
+            for k in outs[0]:
+                assert torch.equal(outs[0][k], outs[1][k]), (it, k)
+
+    two_rollouts(0)
+    before = ags[1]._graph
+    assert before is not None
+    for ag in ags:
+        ag.set_gemm_prec("x3")
+    assert ags[1]._graph is None
+    two_rollouts(2)
+    assert ags[0]._sample_offset == ags[1]._sample_offset
+    assert ags[1]._graph is not None and ags[1]._graph is not before
+
+
 @pytest.mark.parametrize("bootstrap", [False, True])
 def test_batched_rollout_critic_equals_per_step(bootstrap, monkeypatch):
-    """The rollout's critic values from one launch after the env loop (PPO.ROLLOUT_BATCHED_CRITIC, the
+    """The rollout's critic values from one launch after the env loop (rollout.BATCHED_CRITIC, the
     default) are bit-identical to the per-step form (one launch per step, before the step's actions): the
     values depend on the stored observations only and mm_critic_value's arithmetic per row does not depend
     on the rows launched beside it.  Every other buffer of the batch is identical too."""
-    from marlmaze import PPO as ppo_mod
+    from marlmaze import rollout as rollout_mod
 
     cfg = dict(default_size=(6, 6), max_timestep=20, seed_base=11)
     T, n = 8, 512
     outs = []
     for batched in (False, True):
-        monkeypatch.setattr(ppo_mod, "ROLLOUT_BATCHED_CRITIC", batched)
+        monkeypatch.setattr(rollout_mod, "BATCHED_CRITIC", batched)
         ag = _agent(n_envs=n, horizon=T, batch_size=n * T, sample_seed=9, env_config=cfg, bootstrap=bootstrap)
         res = []
         for _ in range(3):
