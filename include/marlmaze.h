@@ -362,6 +362,30 @@ int mm_gemm_wgrad_partials_h(int prec, int flags, const float* dy, int lddy, flo
                              int M, int N, int K, float cscale, float* ws, void* stream);
 int mm_heads_fwd_h16(const void* h, int ldh, int K, const float* w, const float* b, int M, float* logits,
                      void* stream);
+/* x2 plane storage of the MM_PREC_X2 update's hidden activations and input
+ * gradients: fp16 [M][n / 4][2][4] (n % 4 == 0) -- per row and group of four
+ * columns the four hi halves, then the four lo halves, of the split every x2
+ * kernel applies to an fp32 operand anyway (hi = fp16(x s), lo = fp16(2^11
+ * (x s - hi)); s = 1 for activations, the gradient scale for input gradients,
+ * read back at scale 1 with cscale 1 / s).  The same bytes and addresses as the
+ * fp32 matrix (16 bytes per column group; leading dimensions are row pitches
+ * in 4-byte units, multiples of 4, rows 16-byte aligned), the same MFMA
+ * operands, no repeated split; results are bit-identical to fp32 storage.
+ * Replaces nothing in the reference (its networks are fp32, networks.py:31-41).
+ * mm_gemm_nt_h with MM_GEMM_A_X2P: a is such a plane tensor (ascale 1; with
+ *   mbits_in or mbits_out only: the hidden layers' forms);
+ *   MM_GEMM_C_X2P: c likewise (N % 4 == 0), the forward with mbits_out or the
+ *   input gradient with mbits_in (planes of out * oscale).
+ * mm_gemm_wgrad_h / _partials_h with MM_GEMM_A_X2P | MM_GEMM_B_X2P: dy and x
+ *   both plane tensors (dscale 1), at the shapes mm_gemm_x2p_ok accepts
+ *   (the 264 x 264 layers' blocks); other shapes are MM_E_ARG.
+ * mm_x3_heads_bwd_x2p: mm_x3_heads_bwd writing dy as planes of dY * oscale. */
+#define MM_GEMM_A_X2P 8
+#define MM_GEMM_C_X2P 16
+#define MM_GEMM_B_X2P 32
+int mm_gemm_x2p_ok(int M, int N, int K);
+int mm_x3_heads_bwd_x2p(const float* dz, int J, const float* W, const uint32_t* bits, int M, int N, void* dy,
+                        float* colsum, float oscale, void* stream);
 /* mm_actor_front_fwd with h stored fp16 [B, 460] (round to nearest of the fp32
  * values): the f16 networks' update, whose first GEMM (fp16 A at K = 460: the
  * streaming kernel) and its weight gradient round h to fp16 anyway. */

@@ -47,6 +47,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "marlmaze.h"
 #include "policy_device.h"
@@ -165,6 +166,30 @@ __device__ __forceinline__ void pair2(float x0, float x1, float s, uint32_t& h, 
     const f2 r = (v - __builtin_convertvector(hv, f2)) * kX2Lo;
     h = __builtin_bit_cast(uint32_t, hv);
     l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, h2));
+}
+
+// x2 plane storage ("x2p") of an [M, n] activation or input gradient (n % 4 == 0): fp16 [M][n / 4][2][4] --
+// per row and group of four columns the four hi halves, then the four lo halves, of pair2(x, s) of the fp32
+// values that would have been stored (s = 1 for activations, the gradient scale for input gradients, whose
+// consumers then read at scale 1 and apply cscale = 1 / s).  A row is n plane pairs = 4 n bytes, as fp32, and a
+// 16-byte piece (one column group, both planes) sits where the four fp32 values would: every kernel addresses
+// the tensor exactly as the fp32 matrix [M, ld] (ld: the row pitch in 4-byte units, ld % 4 == 0, rows 16-byte
+// aligned for the LDS-DMA and the 16-byte loads).  A GEMM lane's 16-byte A load is its hi and its lo fragment
+// halves; an epilogue lane quad (four adjacent columns of a row) exchanges its (hi, lo) pairs and stores one
+// dword per lane, the addresses of the fp32 store; in LDS the hi piece of a group is 16-byte, the lo piece
+// 8-byte aligned (ds_read_b64_tr_b16 takes 8-byte-aligned pieces of one row).
+__device__ __forceinline__ void pair1(float x, _Float16& h, _Float16& l) {  // pair2 of one value at s = 1
+    h = (_Float16)x;
+    l = (_Float16)((x - (float)h) * kX2Lo);
+}
+// the dword lane (lane & 3) of a column quad stores: [hi0 hi1], [hi2 hi3], [lo0 lo1], [lo2 lo3] of the quad's
+// four (hi, lo) pairs.  Every lane of the quad must be active (DPP quad permutes).
+__device__ __forceinline__ uint32_t x2p_quad_word(_Float16 h, _Float16 l, int lane) {
+    const int p = (int)((uint32_t)__builtin_bit_cast(unsigned short, h) |
+                        ((uint32_t)__builtin_bit_cast(unsigned short, l) << 16));
+    const uint32_t pa = (uint32_t)__builtin_amdgcn_mov_dpp(p, 0x88, 0xF, 0xF, true);  // quad_perm [0, 2, 0, 2]
+    const uint32_t pb = (uint32_t)__builtin_amdgcn_mov_dpp(p, 0xDD, 0xF, 0xF, true);  // quad_perm [1, 3, 1, 3]
+    return __builtin_amdgcn_perm(pb, pa, (lane & 2) ? 0x07060302u : 0x05040100u);  // the lo / the hi halves
 }
 
 // 8 values -> the two 16-byte P_X2 plane pieces
@@ -334,7 +359,8 @@ struct Epi {
     int ldc, ldm, relu, cnks;  // cnks = TP column blocks of the output (ceil(N / 32))
     float cscale;              // P_F16: out = acc * cscale before bias (the inverse of the A scale)
     int bufok;                 // fp32 c (and colsum) addressable through buffer resources (< 2^31 bytes)
-    int c16;                   // c holds fp16 [M, ldc] (EM_FWD16 / EM_BWD16: P_F16's stored activations / gradients)
+    int c16;                   // c holds fp16 [M, ldc] (EM_FWD16 / EM_BWD16: P_F16's stored activations / gradients;
+                               // P_X2: x2 planes, ldc the row pitch in 4-byte units as for fp32)
     float oscale;              // EM_BWD16: c = fp16(out * oscale) (the input gradient pre-scaled for its consumers)
 };
 
@@ -487,6 +513,19 @@ struct ASrcF16V {
     __device__ __forceinline__ void frag(const Raw& r, bf16x8 (&a)[3]) const {
         static_assert(P == P_F16, "fp16 A: P_F16");
         a[0] = __builtin_bit_cast(bf16x8, make_uint4(r[0].x, r[0].y, r[1].x, r[1].y));
+    }
+};
+
+// x2 planes (P_X2 at scale 1; lda: the row pitch in 4-byte units): ASrcF32's loads -- a lane's 16 bytes are
+// the hi halves k .. k + 3, then the lo halves -- and no conversion
+struct ASrcX2PV : ASrcF32V<4> {
+    template <int P>
+    __device__ __forceinline__ void frag(const Raw& r, bf16x8 (&a)[3]) const {
+        static_assert(P == P_X2, "x2 planes: P_X2");
+        a[0] = __builtin_bit_cast(bf16x8, make_uint4(__float_as_uint(r[0].x), __float_as_uint(r[0].y),
+                                                     __float_as_uint(r[1].x), __float_as_uint(r[1].y)));
+        a[1] = __builtin_bit_cast(bf16x8, make_uint4(__float_as_uint(r[0].z), __float_as_uint(r[0].w),
+                                                     __float_as_uint(r[1].z), __float_as_uint(r[1].w)));
     }
 };
 
@@ -676,7 +715,7 @@ __device__ __forceinline__ void bres_epilogue(const f32x4 (&acc)[CT], int rt, in
     int rq = 4 * (lane >> 4);
     asm volatile("" : "+v"(rq));  // offsets formed here, not hoisted over the main loop and held
     const int row0 = 16 * rt + rq, cl = lane & 15;
-    constexpr uint32_t esz = em_16(EM) ? 2u : 4u;  // bytes per output element
+    constexpr uint32_t esz = (em_16(EM) && P != P_X2) ? 2u : 4u;  // bytes per output element (x2 planes: a pair)
     uint32_t voff[4];
 #pragma unroll
     for (int g = 0; g < 4; g++) voff[g] = esz * ((uint32_t)(row0 + g) * (uint32_t)ep.ldc + (uint32_t)cl);
@@ -726,7 +765,15 @@ __device__ __forceinline__ void bres_epilogue(const f32x4 (&acc)[CT], int rt, in
 #ifdef BRES_NO_STORE  // diagnostic builds only
             if (x == 1234.5f)
 #endif
-            if constexpr (em_16(EM)) {
+            if constexpr (em_16(EM) && P == P_X2) {
+                // x2 planes: pair2 of the value (hi past 65504 is inf: the range guard sees it); the column
+                // quad's pairs regrouped, one dword per lane at the fp32 store's address (N % 4 == 0: a quad is
+                // inside N or past it; every lane is active here)
+                _Float16 h, l;
+                pair1(EM == EM_BWD16 ? x * ep.oscale : x, h, l);
+                range_val<P>(rb, (float)h);
+                __builtin_amdgcn_raw_buffer_store_b32(x2p_quad_word(h, l, lane), crs, o, soff, 0);
+            } else if constexpr (em_16(EM)) {
                 // round to nearest; past 65504 it is inf: the range guard sees it
                 const _Float16 h = (_Float16)(EM == EM_BWD16 ? x * ep.oscale : x);
                 range_val<P>(rb, (float)h);
@@ -779,7 +826,7 @@ __global__ __launch_bounds__(SW<P>::kThreads) void k_x3nt(const AT* __restrict__
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (unused when !ep.bufok: then the ranges below are not consulted)
     const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)ep.c, (short)0, (int)((size_t)M * ep.ldc * (EM == EM_FWD16 ? 2 : 4)), 0x00020000);
+        (void*)ep.c, (short)0, (int)((size_t)M * ep.ldc * (em_16(EM) && P != P_X2 ? 2 : 4)), 0x00020000);
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)ep.colsum, (short)0, (int)((size_t)((M + 15) / 16) * N * 4), 0x00020000);
     // workgroup g takes units g, g + G, ...  XCD-aware unit order: units u and
@@ -798,7 +845,7 @@ __global__ __launch_bounds__(SW<P>::kThreads) void k_x3nt(const AT* __restrict__
         AS as;
         as.init(A, rt, nks, M, lda, K, ascale);
         const uint16_t* Bg = B + (size_t)cb * NT * nks * Prec<P>::kBlk;
-        if (EM != EM_BWD && EM != EM_TP && ep.bias && threadIdx.x < 16 * NT) {  // visible after the prologue barrier
+        if (!em_bwd(EM) && EM != EM_TP && ep.bias && threadIdx.x < 16 * NT) {  // visible after the prologue barrier
             int t = threadIdx.x;
             asm volatile("" : "+v"(t));  // recomputed per unit, not a loop-invariant address held (spilled) across it
             const int col = cb * 16 * NT + t;
@@ -829,7 +876,7 @@ __global__ __launch_bounds__(SW<P>::kThreads) void k_x3nt(const AT* __restrict__
         // ---- epilogue (after the last k-step's barrier both stage buffers are free) ----
         if constexpr (EM == EM_TP) {
             epilogue_tp<NT>(acc, reinterpret_cast<float*>(sB0) + wave * 16 * 36, rt, M, N, ep, lane);
-        } else if constexpr (EM == EM_FWD16) {  // (the host requires bufok)
+        } else if constexpr (em_16(EM)) {  // (the host requires bufok)
             bres_epilogue<P, NT, EM>(acc, rt, cb * NT, NT, M, N, ep, crs, srs, sbias, lane);
         } else {
             if (ep.bufok && !ep.mask)  // buffer stores, one code path (bres_epilogue; tiles cb NT .. : even when bits)
@@ -1224,7 +1271,7 @@ __global__ __launch_bounds__(64 * kTrWaves) void k_trunk3(TrunkArgs ta) {
 // per-tile column sums (the last layer's bias gradient, before the final sum).
 // D16: dY stored fp16 as fp16(dY * oscale) (P_F16's pre-scaled input gradients; the sums stay fp32)
 constexpr int kHeadsMaxJ = 8;
-template <int NT, bool D16 = false>
+template <int NT, int D16 = 0>  // D16: 0 fp32 dy, 1 fp16(dy oscale), 2 the x2 planes of dy oscale (row pitch N)
 __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ dz, int J, const float* __restrict__ W,
                                                    const uint32_t* __restrict__ bits, int M, int N,
                                                    float* __restrict__ dy, float* __restrict__ colsum,
@@ -1271,8 +1318,17 @@ __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ dz,
 #pragma unroll
             for (int j = 0; j < kHeadsMaxJ; j++) x = fmaf(z[g][j], sw[j][col], x);
             if (!((b[bit >> 5] >> (bit & 31)) & 1u)) x = 0.f;
+            uint32_t qw = 0u;  // D16 == 2: this lane's dword of its column quad's planes (every lane takes part)
+            if constexpr (D16 == 2) {
+                _Float16 h, l;
+                pair1(x * oscale, h, l);
+                range_val<P_X2>(rb, (float)h);
+                qw = x2p_quad_word(h, l, lane);
+            }
             if (row < M && col < N) {
-                if constexpr (D16) {
+                if constexpr (D16 == 2) {  // (N % 4 == 0: a quad is inside N or past it)
+                    reinterpret_cast<uint32_t*>(dy)[(size_t)row * N + col] = qw;
+                } else if constexpr (D16) {
                     const _Float16 h = (_Float16)(x * oscale);
                     range_val<P_F16>(rb, (float)h);
                     reinterpret_cast<_Float16*>(dy)[(size_t)row * N + col] = h;
@@ -1286,7 +1342,8 @@ __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ dz,
         cs += __shfl_xor(cs, 32);
         if (lane < 16 && col < N) colsum[(size_t)rt * N + col] = cs;
     }
-    if constexpr (D16) range_note_wave<P_F16>(rb);
+    if constexpr (D16 == 2) range_note_wave<P_X2>(rb);
+    else if constexpr (D16) range_note_wave<P_F16>(rb);
 }
 
 
@@ -2100,6 +2157,244 @@ __global__ __launch_bounds__(kWgThreads) void k_wgrad_dma(const float* __restric
     }
 }
 
+// k_wgrad_tr: k_wgrad_dma for operands stored as x2 planes (dY pre-scaled, X at scale 1; see pair1) -- there is
+// nothing to convert.  The plane rows go HBM -> LDS by LDS-DMA into THREE raw stages (the bytes and the
+// addresses per step are k_wgrad_dma's: a plane pair is 4 bytes per element, a 16-byte piece one column group),
+// and the MFMA fragments are read straight from the raw stage with ds_read_b64_tr_b16: for lane l (column
+// l & 15, row group c = l >> 4) the blocks of rows 8c .. 8c + 3 and 8c + 4 .. 8c + 7 of a tile's 16 columns, per
+// plane -- exactly the fragment k_wgrad_dma's image holds, so with the same MFMA order per output tile
+// (mma<P_X2>) the partials are its partials, bit for bit.  No image, no conversion; per step one counted vmcnt
+// wait for this wave's DMAs of that step, ONE barrier (the step's stage visible; the stage of the step before
+// free), the DMA of the step after next.
+//
+// A stage: [A: 32 rows of pitch wpA][B: 32 rows of pitch wpB] in 16-byte pieces, a row holding 4 T pieces (T
+// the operand's tiles) of [4 hi halves][4 lo halves]; wp = 4 T rounded up to 4 mod 16.  Bank rule of the
+// transposed read (64 banks of 4 bytes, conflicts inside a 32-lane half = row groups c, c + 1): lane 4 q + p
+// reads 8 bytes of row q at piece p of the tile, so a plane's read touches only every other 8 bytes -- 32 of
+// the 64 banks -- and two cycles per half are the least this layout allows.  A pitch of 16 mod 64 dwords
+// reaches that: the four rows q of a block take banks 16 q .. 16 q + 15, and rows r and r + 8 the same ones.
+// (Hi and lo in separate LDS rows would read at one cycle, but then a GEMM lane's hi and lo halves lie a row
+// apart in global memory; the stream hides the second cycle here.)
+// Both operands' parts are whole DMA instructions (32 wp pieces, wp % 4 == 0), so an instruction reads one
+// operand.  Columns past an operand's width read the neighbouring row (or zeros past num_records): whatever
+// they hold -- NaN patterns included -- reaches only output rows >= N / columns >= K, which are neither
+// stored nor range-checked.  Rows past the slice arrive as zeros through num_records, for both planes (a piece
+// holds both).  Operand rule as k_wgrad_dma's: one offset set per stage, advanced in place by three steps
+// after its previous DMA was waited for; the resource SGPRs held for the whole kernel.
+constexpr int tr_pitch(int T) {  // 16-byte pieces per staged row
+    int w = 4 * T;
+    while (w % 16 != 4) w++;
+    return w;
+}
+
+template <int TN, int NTK>
+__global__ __launch_bounds__(kWgThreads) void k_wgrad_tr(const uint32_t* __restrict__ dy, int lddy,
+                                                         const uint32_t* __restrict__ x, int ldx, int M, int N, int K,
+                                                         int rows, int nslices, int ncb, float cscale,
+                                                         float* __restrict__ ws) {
+    constexpr int P = P_X2;
+    constexpr int RN = TN / kWgWaves;
+    constexpr int kRem = (TN - kWgWaves * RN) * NTK;
+    constexpr int EX = (kRem + kWgWaves - 1) / kWgWaves;
+    static_assert(RN > 0 && (kRem == 0 || TN - kWgWaves * RN == 1), "leftover tiles of one n-tile (one A fragment)");
+    constexpr int wpA = tr_pitch(TN), wpB = tr_pitch(NTK);  // row pitches, pieces
+    constexpr int kSecA = 32 * wpA, kSecB = 32 * wpB;      // an operand's part of a stage
+    static_assert(kSecA % 64 == 0 && kSecB % 64 == 0, "parts of whole DMA instructions");
+    constexpr int kInsA = kSecA / 64, kInsB = kSecB / 64;  // DMA instructions per part
+    constexpr int kStage = kSecA + kSecB;                  // pieces
+    constexpr int kStages = 3;
+    static_assert(kStages * kStage * 16 <= 160 * 1024, "LDS");
+    __shared__ __attribute__((aligned(16))) uint4 raw[kStages * kStage];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int s = (slot / ncb) * 8 + xcd, cb = slot % ncb;
+    if (s >= nslices) return;  // the whole workgroup
+    const int m_begin = s * rows, nrows = min(M, m_begin + rows) - m_begin;
+    const int col0 = cb * NTK * 16;
+    __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(dy + (size_t)m_begin * lddy), (short)0, (int)(nrows * lddy * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(x + (size_t)m_begin * ldx + col0), (short)0, (int)((nrows * ldx - col0) * 4), 0x00020000);
+    asm volatile("" : "+s"(rsA));
+    asm volatile("" : "+s"(rsB));
+
+    // this wave's DMA instructions: of the kInsA instructions of dY a = wave + 8 k, of the kInsB of X
+    // b = wave + 8 k -- the operand of offset slot k is a compile-time fact, so each DMA names rsA or rsB
+    // directly (a selected copy would be rewritten while earlier DMAs are in flight).  The lane's piece -> its
+    // byte offset in step t of offset set t; unused pieces (row padding): out of range
+    constexpr int kSlotA = (kInsA + kWgWaves - 1) / kWgWaves, kSlotB = (kInsB + kWgWaves - 1) / kWgWaves;
+    auto lane_off = [&](int j, bool isA, int t) {  // instruction j of an operand's part
+        const int e = 64 * j + lane;  // piece inside the part
+        const int wp = isA ? wpA : wpB, T4 = isA ? 4 * TN : 4 * NTK;
+        const int r = e / wp, c = e % wp;
+        const int ld = isA ? lddy : ldx;
+        return c < T4 ? (uint32_t)(((32 * t + r) * ld + 4 * c) * 4) : kBufOOB;
+    };
+    uint32_t obA[kStages][kSlotA], obB[kStages][kSlotB];
+#pragma unroll
+    for (int k = 0; k < kSlotA; k++) {
+        const int a = min(wave + kWgWaves * k, kInsA - 1);  // (clamped: not issued)
+#pragma unroll
+        for (int t = 0; t < kStages; t++) {
+            obA[t][k] = lane_off(a, true, t);
+            asm volatile("" : "+v"(obA[t][k]));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kSlotB; k++) {
+        const int bi = min(wave + kWgWaves * k, kInsB - 1);
+#pragma unroll
+        for (int t = 0; t < kStages; t++) {
+            obB[t][k] = lane_off(bi, false, t);
+            asm volatile("" : "+v"(obB[t][k]));
+        }
+    }
+    const uint32_t stepA = (uint32_t)kStages * 32u * (uint32_t)lddy * 4u, stepB = (uint32_t)kStages * 32u * (uint32_t)ldx * 4u;
+    auto issue = [&](auto tc, int st) {  // the DMA of step st into raw stage T (offset set T)
+        constexpr int T = decltype(tc)::value;
+        const uint32_t base = lds_addr(raw + T * kStage);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < kSlotA; k++) {
+            const int a = wave + kWgWaves * k;  // wave-uniform
+            if (a < kInsA) {
+                if (st >= kStages) asm volatile("v_add_u32 %0, %0, %1" : "+v"(obA[T][k]) : "s"(stepA));
+                dma16(rsA, obA[T][k], base + 1024u * (uint32_t)a);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kSlotB; k++) {
+            const int bi = wave + kWgWaves * k;
+            if (bi < kInsB) {
+                if (st >= kStages) asm volatile("v_add_u32 %0, %0, %1" : "+v"(obB[T][k]) : "s"(stepB));
+                dma16(rsB, obB[T][k], base + 16u * (uint32_t)kSecA + 1024u * (uint32_t)bi);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // instructions per wave and step: the count a wave may leave in flight (the next step's)
+    constexpr int kRemA = kInsA % kWgWaves, kRemB = kInsB % kWgWaves;
+    static_assert(kRemA == kRemB && kRemA != 0, "waves below kRemA issue one more instruction of each operand");
+    constexpr int kInsW = kSlotA + kSlotB, kInsWmin = kInsW - 2;
+    // this wave's DMAs of the step about to be read have landed; only the next step's may be in flight
+    auto wait_stage = [&](bool later_in_flight) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (later_in_flight) {
+            if (wave < kRemA) {
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (kInsW & 15) | ((kInsW >> 4) << 14));
+            } else {
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (kInsWmin & 15) | ((kInsWmin >> 4) << 14));
+            }
+        } else {
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");
+    };
+    auto barrier = [&]() {  // this wave's LDS reads done; every wave's DMAs of the step visible (waited for above)
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt((15 << 0) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // the transposed read: lane 4 q + p of row group c supplies row 8 c + q, piece p of the tile (its four
+    // columns 4 p .. 4 p + 3: the hi halves, 8 bytes on the lo halves)
+    const int tc = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+    const uint32_t laneA = (uint32_t)(16 * ((8 * tc + tq) * wpA + tp));           // bytes
+    const uint32_t laneB = (uint32_t)(16 * (kSecA + (8 * tc + tq) * wpB + tp));
+    typedef short s4v __attribute__((ext_vector_type(4)));
+    auto tr = [&](const char* p) {
+        return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(p));
+    };
+    auto frag = [&](const char* stage, bool isA, uint32_t lbase, int tile, bf16x8 (&f)[3]) {
+        const char* p = stage + lbase + 64 * tile;
+        const int r4 = 16 * 4 * (isA ? wpA : wpB);  // four rows on, bytes
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const s4v u = tr(p + 8 * q), v = tr(p + 8 * q + r4);
+            f[q] = bf16x8{u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+        }
+    };
+
+    f32x4 acc[RN * NTK + EX], accx[RN * NTK + EX];
+#pragma unroll
+    for (int u = 0; u < RN * NTK + EX; u++) acc[u] = accx[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nsteps = (nrows + 31) / 32;
+    constexpr std::integral_constant<int, 0> c0{};
+    constexpr std::integral_constant<int, 1> c1{};
+    constexpr std::integral_constant<int, 2> c2{};
+    issue(c0, 0);
+    if (nsteps > 1) issue(c1, 1);
+    auto step = [&](auto tcur, auto tnext2, int st) {  // step st in stage T; step st + 2 goes to stage (T + 2) % 3
+        constexpr int T = decltype(tcur)::value;
+        wait_stage(st + 1 < nsteps);
+        barrier();
+        if (st + 2 < nsteps) issue(tnext2, st + 2);
+        const char* stage = reinterpret_cast<const char*>(raw + T * kStage);
+        bf16x8 a[RN][3], ax[3], b[2][3];
+#pragma unroll
+        for (int r = 0; r < RN; r++) frag(stage, true, laneA, RN * wave + r, a[r]);
+        if constexpr (EX > 0) frag(stage, true, laneA, kWgWaves * RN, ax);  // the leftover tiles' n-tile
+        frag(stage, false, laneB, 0, b[0]);
+#pragma unroll
+        for (int tk = 0; tk < NTK; tk++) {
+            if (tk + 1 < NTK) frag(stage, false, laneB, tk + 1, b[(tk + 1) & 1]);
+#pragma unroll
+            for (int r = 0; r < RN; r++)
+                acc[r * NTK + tk] = mma<P>(a[r], b[tk & 1], acc[r * NTK + tk], accx[r * NTK + tk]);
+        }
+#pragma unroll
+        for (int e = 0; e < EX; e++) {
+            int j = wave + kWgWaves * e;  // leftover tile j (clamped: a duplicate, not stored)
+            j = j < kRem ? j : kRem - 1;
+            bf16x8 b1[3];
+            frag(stage, false, laneB, j % NTK, b1);
+            acc[RN * NTK + e] = mma<P>(ax, b1, acc[RN * NTK + e], accx[RN * NTK + e]);
+        }
+    };
+    for (int st = 0; st < nsteps; st += 3) {
+        step(c0, c2, st);
+        if (st + 1 < nsteps) step(c1, c0, st + 1);
+        if (st + 2 < nsteps) step(c2, c1, st + 2);
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (every issued DMA was waited for before its step)
+#pragma unroll
+    for (int t = 0; t < kStages; t++) {
+#pragma unroll
+        for (int k = 0; k < kSlotA; k++) asm volatile("" ::"v"(obA[t][k]));
+#pragma unroll
+        for (int k = 0; k < kSlotB; k++) asm volatile("" ::"v"(obB[t][k]));
+    }
+    asm volatile("" ::"s"(rsA), "s"(rsB), "s"(stepA), "s"(stepB));
+    uint32_t rm = 0;  // the range guard, over the stored accumulators only (the others may hold anything)
+    float* out = ws + (size_t)s * N * K;
+    auto put = [&](f32x4 v, f32x4 vx, int tn, int tk) {
+        v = x2_combine<P>(v, vx);
+        const int col = col0 + 16 * tk + (lane & 15);
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int row = 16 * tn + 4 * (lane >> 4) + g;
+            if (row < N && col < K) {
+                rm = max(rm, __float_as_uint(v[g]) & 0x7FFFFFFFu);
+                out[(size_t)row * K + col] = v[g] * cscale;
+            }
+        }
+    };
+#pragma unroll
+    for (int r = 0; r < RN; r++)
+#pragma unroll
+        for (int tk = 0; tk < NTK; tk++) put(acc[r * NTK + tk], accx[r * NTK + tk], RN * wave + r, tk);
+#pragma unroll
+    for (int e = 0; e < EX; e++) {
+        const int j = wave + kWgWaves * e;
+        if (j < kRem) put(acc[RN * NTK + e], accx[RN * NTK + e], kWgWaves * RN + j / NTK, j % NTK);
+    }
+    range_note<P>(rm);
+}
+
 // out[e] = sum over the row slices s of ws[s][e]: 16 groups of consecutive slices per element, each group's
 // loads all in flight (the plain per-element loop over S = 256 slices was latency-bound: ~90 us), the
 // groups then summed in order -- a fixed order, so the result is deterministic
@@ -2203,7 +2498,9 @@ __device__ __forceinline__ void bres_load(const BresA& as, int ks, int K, int kq
                 continue;
             }
             const uint32_t o = as.roff[r] + 4u * (32 * ks + 16 * h);
-            if constexpr (VW == 4) {
+            // (VW 32, x2 planes: fp32 A's 16-byte load -- raw[.][h] = [hi k .. k + 3][lo k .. k + 3]; bres_frag
+            // regroups the two pieces into the hi and the lo fragment in place)
+            if constexpr (VW == 4 || VW == 32) {
                 const u32x4v v = __builtin_amdgcn_raw_buffer_load_b128(as.rsrc, kk < K ? o : kBufOOB, 0, 0);
                 raw[r][h] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
                                         __uint_as_float(v.w));
@@ -2223,6 +2520,22 @@ __device__ __forceinline__ void bres_frag(const float4 (&r)[2], float s, bf16x8 
     if constexpr (VW == 16) {  // fp16 A (P_F16, scale 1): the loaded halves are the fragment
         a[0] = __builtin_bit_cast(bf16x8, make_uint4(__float_as_uint(r[0].x), __float_as_uint(r[0].y),
                                                      __float_as_uint(r[0].z), __float_as_uint(r[0].w)));
+        return;
+    }
+    if constexpr (VW == 32) {
+        // x2 planes (scale 1): r[0] = [hi k ..][lo k ..], r[1] = [hi k + 16 ..][lo k + 16 ..] -> the hi fragment
+        // (r[0].xy, r[1].xy) and the lo fragment (r[0].zw, r[1].zw).  Two register swaps in the raw registers
+        // themselves (dead after this step until reloaded: the callers' raw sets are their own locals), so an
+        // MFMA operand is a loaded register quadruple and no copy of the eight is held
+        static_assert(P == P_X2, "x2 planes: P_X2");
+        float4(&m)[2] = const_cast<float4(&)[2]>(r);
+        // (the two wait states between a VALU write and an MFMA reading it as an operand: inside the string)
+        asm("v_swap_b32 %0, %2\n\tv_swap_b32 %1, %3\n\ts_nop 1"
+            : "+v"(m[0].z), "+v"(m[0].w), "+v"(m[1].x), "+v"(m[1].y));
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+            a[q] = __builtin_bit_cast(bf16x8, make_uint4(__float_as_uint(m[q].x), __float_as_uint(m[q].y),
+                                                         __float_as_uint(m[q].z), __float_as_uint(m[q].w)));
         return;
     }
 #ifdef BRES_NO_SPLIT  // diagnostic builds only: the raw bits as fragments (no split VALU; outputs wrong)
@@ -2258,9 +2571,15 @@ __device__ __forceinline__ void bres_frag(const float4 (&r)[2], float s, bf16x8 
 
 // the final 16-wide step: the 4 values k = 4 (l >> 4) .. +3 (the j < 4 half of a TP piece)
 template <int P, int VW>
-__device__ __forceinline__ void bres_frag16(const float4& r, float s, uint2 (&a)[3]) {
+__device__ __forceinline__ void bres_frag16(const float4 (&rr)[2], float s, uint2 (&a)[3]) {
+    const float4& r = rr[0];  // (fp32 / fp16 A: the 16-byte piece of the j < 4 half)
     if constexpr (VW == 16) {  // fp16 A: the j < 4 half is the first 8 bytes
         a[0] = make_uint2(__float_as_uint(r.x), __float_as_uint(r.y));
+        return;
+    }
+    if constexpr (VW == 32) {  // x2 planes: the piece is [hi k .. k + 3][lo k .. k + 3]
+        a[0] = make_uint2(__float_as_uint(r.x), __float_as_uint(r.y));
+        a[1] = make_uint2(__float_as_uint(r.z), __float_as_uint(r.w));
         return;
     }
     if constexpr (P == P_X3) {
@@ -2369,6 +2688,7 @@ __global__ __launch_bounds__(64 * kBresWaves) void k_bres(const float* __restric
                                                    BresPlan pl, Epi ep) {
     static_assert(EM == EM_F32 || em_fwd(EM) || em_bwd(EM), "row-major outputs");
     static_assert(VW != 16 || P == P_F16, "fp16 A: P_F16");
+    static_assert(VW != 32 || P == P_X2, "x2 planes A: P_X2");
     constexpr int np = Prec<P>::kPlanes;
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     const int lane = threadIdx.x & 63;
@@ -2418,11 +2738,11 @@ __global__ __launch_bounds__(64 * kBresWaves) void k_bres(const float* __restric
     const int nsb = (ctb + CT - 1) / CT;
     const int kq = 4 * (lane >> 4);
     // gfx9 buffer resource word 3 0x00020000: 32-bit data format, raw (stride 0) addressing
-    constexpr uint32_t aesz = VW == 16 ? 2u : 4u;  // VW 16: A is fp16 [M, lda]
+    constexpr uint32_t aesz = VW == 16 ? 2u : 4u;  // VW 16: A is fp16 [M, lda] (32: x2 planes, a pair per element)
     const __amdgpu_buffer_rsrc_t arsrc =
         __builtin_amdgcn_make_buffer_rsrc((void*)A, (short)0, (int)((size_t)M * lda * aesz), 0x00020000);
     const __amdgpu_buffer_rsrc_t crs =  // C [M, ldc]: rows past M past num_records
-        __builtin_amdgcn_make_buffer_rsrc((void*)ep.c, (short)0, (int)((size_t)M * ep.ldc * (em_16(EM) ? 2 : 4)),
+        __builtin_amdgcn_make_buffer_rsrc((void*)ep.c, (short)0, (int)((size_t)M * ep.ldc * (em_16(EM) && P != P_X2 ? 2 : 4)),
                                           0x00020000);
     const __amdgpu_buffer_rsrc_t srs =  // colsum [ceil(M / 16), N]
         __builtin_amdgcn_make_buffer_rsrc((void*)ep.colsum, (short)0, (int)((size_t)((M + 15) / 16) * N * 4),
@@ -2469,7 +2789,7 @@ __global__ __launch_bounds__(64 * kBresWaves) void k_bres(const float* __restric
                 if (half) {  // step nfull is in A (rem 0), B (rem 1) or C (rem 2)
 #pragma unroll
                     for (int r = 0; r < RT; r++)
-                        bres_frag16<P, VW>(rem == 0 ? rA[r][0] : rem == 1 ? rB[r][0] : rC[r][0], ascale, a4[r]);
+                        bres_frag16<P, VW>(rem == 0 ? rA[r] : rem == 1 ? rB[r] : rC[r], ascale, a4[r]);
                 }
             } else {
                 float4 rawA[RT][2], rawB[RT][2];
@@ -2483,7 +2803,7 @@ __global__ __launch_bounds__(64 * kBresWaves) void k_bres(const float* __restric
                 if (odd) bres_step<P, CT, RT, VW>(acc, accx, rawA, rawB, as, ks, K, kq, ctb, c0, ctn, ascale, sF, lane);
                 if (half) {
 #pragma unroll
-                    for (int r = 0; r < RT; r++) bres_frag16<P, VW>(odd ? rawB[r][0] : rawA[r][0], ascale, a4[r]);
+                    for (int r = 0; r < RT; r++) bres_frag16<P, VW>(odd ? rawB[r] : rawA[r], ascale, a4[r]);
                 }
             }
             if (half) {
@@ -2629,6 +2949,16 @@ static int launch_nt(const AT* a, int lda, float ascale, const uint16_t* b, int 
                                K, nks, nrb, ncb, ep);
             return (int)hipGetLastError();
         }
+        if constexpr (P == P_X2 && !std::is_same<AS, ASrcF32U>::value) {  // x2 planes out: forward or input gradient
+            if ((!ep.mbits_out && !ep.mbits_in) || !ep.bufok) return MM_E_ARG;
+            if (ep.mbits_out)
+                hipLaunchKernelGGL((k_x3nt<NT, P, AS, AT, EM_FWD16>), dim3(grid), dim3(kT), 0, s, a, lda, ascale, b,
+                                   M, N, K, nks, nrb, ncb, ep);
+            else
+                hipLaunchKernelGGL((k_x3nt<NT, P, AS, AT, EM_BWD16>), dim3(grid), dim3(kT), 0, s, a, lda, ascale, b,
+                                   M, N, K, nks, nrb, ncb, ep);
+            return (int)hipGetLastError();
+        }
         return MM_E_ARG;
     }
     if (ep.mbits_out)
@@ -2637,6 +2967,8 @@ static int launch_nt(const AT* a, int lda, float ascale, const uint16_t* b, int 
     else if (ep.mbits_in)
         hipLaunchKernelGGL((k_x3nt<NT, P, AS, AT, EM_BWD>), dim3(grid), dim3(kT), 0, s, a, lda, ascale, b, M, N,
                            K, nks, nrb, ncb, ep);
+    else if constexpr (std::is_same<AS, ASrcX2PV>::value)
+        return MM_E_ARG;  // x2 planes A: the hidden layers' forms only (with bits)
     else
         hipLaunchKernelGGL((k_x3nt<NT, P, AS, AT, EM_F32>), dim3(grid), dim3(kT), 0, s, a, lda, ascale, b, M, N,
                            K, nks, nrb, ncb, ep);
@@ -2668,7 +3000,11 @@ static int dispatch_nt(const AT* a, int lda, float ascale, const uint16_t* b_tp,
         case 1: return launch_nt<1, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
         case 4: return launch_nt<4, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
         case 8: return launch_nt<8, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
-        case 15: return launch_nt<15, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
+        case 15:
+            if constexpr (std::is_same<AS, ASrcX2PV>::value)
+                return MM_E_ARG;  // (plane A comes with bits: N <= 272, one block)
+            else
+                return launch_nt<15, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
         default: return launch_nt<17, P, AS>(a, lda, ascale, b_tp, M, N, K, ncb, ep, s);
     }
 }
@@ -2819,7 +3155,7 @@ template <int P, int C, int VW>
 static int dispatch_bres_c(const float* a, int lda, float ascale, const uint16_t* b, int M, int N, int K,
                            const BresPlan& pl, const Epi& ep, hipStream_t s) {
     if (ep.c16) {
-        if constexpr (P == P_F16) {
+        if constexpr (P == P_F16 || (P == P_X2 && VW != 2)) {  // fp16 out (P_F16) / x2 planes out (P_X2)
             if (ep.mbits_out) return launch_bres<P, C, EM_FWD16, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
             if (ep.mbits_in) return launch_bres<P, C, EM_BWD16, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
         }
@@ -2827,7 +3163,10 @@ static int dispatch_bres_c(const float* a, int lda, float ascale, const uint16_t
     }
     if (ep.mbits_out) return launch_bres<P, C, EM_FWD, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
     if (ep.mbits_in) return launch_bres<P, C, EM_BWD, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
-    return launch_bres<P, C, EM_F32, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
+    if constexpr (VW == 32)
+        return MM_E_ARG;  // x2 planes A: the hidden layers' forms only (with bits)
+    else
+        return launch_bres<P, C, EM_F32, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
 }
 
 template <int P, int VW>
@@ -2872,8 +3211,48 @@ static int gemm_nt_f32a(int prec, const float* a, int lda, float ascale, const u
     int e = check_common(b_tp, M, N, K, mask, ldm, c, ldc, c_tp);
     if (e) return e;
     if (prec != MM_PREC_X3 && prec != MM_PREC_F16 && prec != MM_PREC_X2) return MM_E_ARG;
+    // x2 planes (P_X2): a / c addressed exactly as the fp32 matrices (lda / ldc in 4-byte units)
+    const bool ap = flags & MM_GEMM_A_X2P, cp = flags & MM_GEMM_C_X2P;
     const bool a16 = flags & MM_GEMM_A_F16, c16 = flags & MM_GEMM_C_F16;
-    if (flags & ~(MM_GEMM_A_F16 | MM_GEMM_C_F16)) return MM_E_ARG;
+    if (flags & ~(MM_GEMM_A_F16 | MM_GEMM_C_F16 | MM_GEMM_A_X2P | MM_GEMM_C_X2P)) return MM_E_ARG;
+    if (ap || cp) {
+        if (prec != MM_PREC_X2 || mask || c_tp || a16 || c16) return MM_E_ARG;
+        if (!a || (K & 3) || (lda & 3) || lda < K || ((uintptr_t)a & 15)) return MM_E_ARG;  // 16-byte rows
+        if (ap && (ascale != 1.f || (!mbits_in && !mbits_out))) return MM_E_ARG;  // (plane A: through ReLU bits)
+        if (cp && ((!mbits_out && !mbits_in) || (N & 3) || (ldc & 3) || ((uintptr_t)c & 15))) return MM_E_ARG;
+        if ((mbits_in || mbits_out) && (N > 16 * 17 || (mbits_in && mbits_out))) return MM_E_ARG;
+        if (mbits_in && (bias || relu)) return MM_E_ARG;
+        if (colsum && (!mbits_in || !c)) return MM_E_ARG;
+        if (M == 0) return 0;
+        const size_t wmaxp = std::max(std::max((size_t)lda, (size_t)ldc), (size_t)N);
+        const size_t capp = ((((size_t)1 << 31) - 1) / (4 * wmaxp) - 32) / kRowPad * kRowPad;
+        if ((size_t)M > capp) {  // row chunks, as below
+            if (capp < (size_t)kRowPad) return MM_E_ARG;
+            for (size_t m0 = 0; m0 < (size_t)M; m0 += capp) {
+                const int mr = (int)std::min(capp, (size_t)M - m0);
+                const size_t rt0 = m0 / 16;
+                const int rc = gemm_nt_f32a(prec, a + m0 * lda, lda, ascale, b_tp, mr, N, K, bias, relu, nullptr, 0,
+                                            mbits_in ? mbits_in + rt0 * 64 * kMaskWords : nullptr,
+                                            mbits_out ? mbits_out + rt0 * 64 * kMaskWords : nullptr,
+                                            colsum ? colsum + rt0 * N : nullptr, cscale, c + m0 * ldc, ldc, nullptr,
+                                            stream, flags, oscale);
+                if (rc) return rc;
+            }
+            return 0;
+        }
+        Epi epp{bias, nullptr, mbits_in, mbits_out, c, nullptr, colsum, ldc, 0, relu, rup(N, 32) / 32, cscale, 1,
+                cp ? 1 : 0, oscale};
+        hipStream_t sp = (hipStream_t)stream;
+        BresPlan plp;
+        int cfgp = C_PAIR;
+        // the kernel choice of the fp32-storage call below (same plan, same row chunks)
+        const bool bres = bres_enabled() && bres_plan(prec, M, N, K, lda, ldc, mbits_in || mbits_out, plp, cfgp);
+        if (ap)
+            return bres ? dispatch_bres<P_X2, 32>(a, lda, 1.f, b_tp, M, N, K, plp, cfgp, epp, sp)
+                        : dispatch_nt<P_X2, ASrcX2PV>(a, lda, 1.f, b_tp, M, N, K, epp, sp);
+        return bres ? dispatch_bres<P_X2, 4>(a, lda, ascale, b_tp, M, N, K, plp, cfgp, epp, sp)
+                    : dispatch_nt<P_X2, ASrcF32>(a, lda, ascale, b_tp, M, N, K, epp, sp);
+    }
     // fp16 activations (P_F16 only): A fp16 at scale 1 on the B-resident kernel; C fp16 for the forward with bits
     if ((a16 || c16) && (prec != MM_PREC_F16 || mask || c_tp)) return MM_E_ARG;
     if (a16 && (ascale != 1.f || (K & 3) || (lda & 3) || ((uintptr_t)a & 7))) return MM_E_ARG;
@@ -3097,6 +3476,18 @@ extern "C" int mm_trunk3_head_sample(int prec, const float* h0, int lda, int M, 
 // dY = (dz W) * bits (the heads' backward through the last ReLU, bits from the
 // last forward GEMM's mbits_out, N <= 272, J <= 8), and the per-16-row-tile
 // column sums colsum [ceil(M / 16), N].
+// the same with dY as x2 planes of dY * oscale (P_X2's pre-scaled input gradients, [M][N / 4][2][4] fp16)
+extern "C" int mm_x3_heads_bwd_x2p(const float* dz, int J, const float* W, const uint32_t* bits, int M, int N,
+                                   void* dy, float* colsum, float oscale, void* stream) {
+    if (!dz || !W || !bits || !dy || !colsum || J <= 0 || J > kHeadsMaxJ || N <= 0 || N > 272 || (N & 3) || M < 0)
+        return MM_E_ARG;
+    if (M == 0) return 0;
+    const int nrt = (M + 15) / 16;
+    hipLaunchKernelGGL((k_heads_bwd<17, 2>), dim3((nrt + 3) / 4), dim3(256), 0, (hipStream_t)stream, dz, J, W, bits,
+                       M, N, static_cast<float*>(dy), colsum, oscale);
+    return (int)hipGetLastError();
+}
+
 // the same with dY fp16 = fp16(dY * oscale) (P_F16's pre-scaled input gradients)
 extern "C" int mm_x3_heads_bwd_h16(const float* dz, int J, const float* W, const uint32_t* bits, int M, int N,
                                    void* dy, float* colsum, float oscale, void* stream) {
@@ -3104,7 +3495,7 @@ extern "C" int mm_x3_heads_bwd_h16(const float* dz, int J, const float* W, const
         return MM_E_ARG;
     if (M == 0) return 0;
     const int nrt = (M + 15) / 16;
-    hipLaunchKernelGGL((k_heads_bwd<17, true>), dim3((nrt + 3) / 4), dim3(256), 0, (hipStream_t)stream, dz, J, W, bits,
+    hipLaunchKernelGGL((k_heads_bwd<17, 1>), dim3((nrt + 3) / 4), dim3(256), 0, (hipStream_t)stream, dz, J, W, bits,
                        M, N, static_cast<float*>(dy), colsum, oscale);
     return (int)hipGetLastError();
 }
@@ -3248,6 +3639,17 @@ static int launch_dma_t(const WgPlan& p, const float* dy, int lddy, float dscale
     return (int)hipGetLastError();
 }
 
+// the plane-operand kernel (k_wgrad_tr): dY and X as x2 planes, lddy / ldx their row pitches in 4-byte units
+template <int TN, int NTK>
+static int launch_tr_t(const WgPlan& p, const uint32_t* dy, int lddy, const uint32_t* x, int ldx, int M, int N, int K,
+                       float cscale, float* ws, hipStream_t s) {
+    hipLaunchKernelGGL((k_wgrad_tr<TN, NTK>), dim3(rup(p.nslices, 8) * p.ncb), dim3(kWgThreads), 0, s, dy, lddy, x,
+                       ldx, M, N, K, p.rows, p.nslices, p.ncb, cscale, ws);
+    return (int)hipGetLastError();
+}
+
+static bool wg_x2p_shape(const WgPlan& p) { return p.TN == 17 && p.NTK == 9; }  // the 264 x 264 layers' blocks
+
 template <int P, int XB = 4, int AB = 4>
 static int launch_rect_p(const WgPlan& p, const float* dy, int lddy, float dscale, const float* x, int ldx, int M,
                          int N, int K, float cscale, float* ws, hipStream_t s) {
@@ -3297,8 +3699,26 @@ static int launch_wgrad_rect(int prec, const WgPlan& p, const float* dy, int ldd
 static int gemm_wgrad(int prec, const float* dy, int lddy, float dscale, const float* x, int ldx, int M, int N, int K,
                       float cscale, float* ws, float* dw, void* stream, int flags = 0) {
     if (M < 0 || N <= 0 || K <= 0 || N > 16 * kWgMaxT || lddy < N || ldx < K) return MM_E_ARG;
-    if (flags & ~(MM_GEMM_B_F16 | MM_GEMM_A_F16)) return MM_E_ARG;
+    if (flags & ~(MM_GEMM_B_F16 | MM_GEMM_A_F16 | MM_GEMM_A_X2P | MM_GEMM_B_X2P)) return MM_E_ARG;
     const bool x16 = flags & MM_GEMM_B_F16, a16 = flags & MM_GEMM_A_F16;  // a16: dY fp16 (pre-scaled)
+    if (flags & (MM_GEMM_A_X2P | MM_GEMM_B_X2P)) {  // both operands as x2 planes (dY pre-scaled: dscale 1): k_wgrad_tr
+        if (flags != (MM_GEMM_A_X2P | MM_GEMM_B_X2P) || prec != MM_PREC_X2 || dscale != 1.f) return MM_E_ARG;
+        hipStream_t sp = (hipStream_t)stream;
+        if (M == 0) return dw ? (int)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, sp) : MM_E_ARG;
+        if (!dy || !x || !ws || (N & 3) || (K & 3) || (lddy & 3) || (ldx & 3) ||
+            (((uintptr_t)dy | (uintptr_t)x) & 15) || (size_t)M * lddy * 4 >= ((size_t)1 << 31) ||
+            (size_t)M * ldx * 4 >= ((size_t)1 << 31))
+            return MM_E_ARG;
+        const WgPlan pp = wg_plan(prec, M, N, K);
+        if (!wg_x2p_shape(pp)) return MM_E_ARG;
+        const uint32_t* dyp = reinterpret_cast<const uint32_t*>(dy);
+        const uint32_t* xp = reinterpret_cast<const uint32_t*>(x);
+        const int ep = launch_tr_t<17, 9>(pp, dyp, lddy, xp, ldx, M, N, K, cscale, ws, sp);
+        if (ep || !dw) return ep;
+        const long np = (long)N * K;
+        hipLaunchKernelGGL(k_wg_reduce, dim3((unsigned)((np + 15) / 16)), dim3(256), 0, sp, ws, pp.nslices, np, dw);
+        return (int)hipGetLastError();
+    }
     if (prec != MM_PREC_X3 && prec != MM_PREC_F16 && prec != MM_PREC_X2) return MM_E_ARG;
     if (prec == MM_PREC_X3 && (dscale != 1.f || cscale != 1.f)) return MM_E_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -3342,6 +3762,15 @@ extern "C" int mm_gemm_a16_ok(int M, int N, int K, int lda, int ldc) {
     BresPlan pl;
     int cfg = C_NARROW;
     return bres_enabled() && bres_plan(MM_PREC_F16, M, N, K, lda, ldc, true, pl, cfg) ? 1 : 0;
+}
+
+// whether the x2 trunk shape [M, K] -> [M, N] takes plane storage end to end: the weight gradient dW [N, K]
+// has k_wgrad_tr's blocks and the plane rows fit the kernels' buffer resources (the GEMMs take planes at
+// every shape of P_X2)
+extern "C" int mm_gemm_x2p_ok(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0 || N > 16 * kWgMaxT || (N & 3) || (K & 3)) return 0;
+    if ((size_t)(M + 16) * std::max(N, K) * 4 >= ((size_t)1 << 31)) return 0;
+    return wg_x2p_shape(wg_plan(MM_PREC_X2, M, N, K)) ? 1 : 0;
 }
 
 extern "C" int mm_gemm_wgrad_slices(int prec, int M, int N, int K) {

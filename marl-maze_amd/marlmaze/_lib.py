@@ -69,7 +69,8 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_trunk3_head_sample_ok", "mm_trunk3_head_sample", "mm_actor_front_fwd_h16",
            "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum",
            "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum",
-           "mm_elog_state_words", "mm_elog_init", "mm_elog_start", "mm_elog_step")
+           "mm_elog_state_words", "mm_elog_init", "mm_elog_start", "mm_elog_step",
+           "mm_gemm_x2p_ok", "mm_x3_heads_bwd_x2p")
 VERSION = 308  # mm_version() this binding is written for
 
 PREC_X3, PREC_F16, PREC_X2 = 0, 1, 2  # MM_PREC_*
@@ -77,6 +78,7 @@ FRONT_BWD = {"mfma": 0, "valu": 1}  # MM_FRONT_BWD_*
 FRONT_FWD = {"row1": 0, "row2": 1, "mfma": 2}  # MM_FRONT_FWD_*
 GEMM_ALGO = {"auto": 0, "stream": 1}  # MM_GEMM_*
 GEMM_A_F16, GEMM_C_F16, GEMM_B_F16 = 1, 2, 4  # MM_GEMM_A_F16 / _C_F16 / _B_F16
+GEMM_A_X2P, GEMM_C_X2P, GEMM_B_X2P = 8, 16, 32  # MM_GEMM_A_X2P / _C_X2P / _B_X2P (x2 plane storage)
 
 
 class EnvDesc(ctypes.Structure):
@@ -122,7 +124,25 @@ class WsumSeg(ctypes.Structure):
 _LIB = None
 
 
+class _Lib:
+    """The loaded library: an export this binding calls but the library lacks (an older build given through
+    MARLMAZE_LIB) raises MMError, not AttributeError.  hasattr() stays False for it."""
+
+    def __init__(self, cdll):
+        self._cdll = cdll
+
+    def __getattr__(self, name):
+        try:
+            return getattr(self._cdll, name)
+        except AttributeError:
+            raise _MissingExport(f"{LIB_PATH} has no export {name}: rebuild the library") from None
+
+
 class MMError(RuntimeError):
+    pass
+
+
+class _MissingExport(MMError, AttributeError):
     pass
 
 
@@ -142,7 +162,7 @@ def lib():
                     f"{LIB_PATH} was not built from the sources in this tree (its {os.path.basename(_build.HASH_FILE)} "
                     "is missing or differs from the sha256 of csrc/ + include/): rebuild it with "
                     "`python -c 'import __graft_entry__ as g; g.build()'`")
-        L = ctypes.CDLL(LIB_PATH)
+        L = _Lib(ctypes.CDLL(LIB_PATH))
         P, i32, u64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_float
         L.mm_version.restype = i32
         L.mm_layout_stride.argtypes = [i32] * 5
@@ -264,6 +284,8 @@ def lib():
                            ("mm_trunk3_head_sample_ok", [i32, i32, i32, i32, i32, i32, i32]),
                            ("mm_actor_front_fwd_h16", [P, P, i32, i32, i32, P, P]),
                            ("mm_actor_front_fwd_h16_ex", [P, P, i32, i32, i32, P, i32, P]),
+                           ("mm_gemm_x2p_ok", [i32, i32, i32]),
+                           ("mm_x3_heads_bwd_x2p", [P, i32, P, P, i32, i32, P, P, f32, P]),
                            ("mm_trunk3_head_sample", [i32, P, i32, i32, i32, P, P, i32, P, P, i32, P, P, i32, P, P, P,
                                                       u64, u64, P, P, P, P, P, P, i32, P])):
             if hasattr(L, name):

@@ -215,11 +215,14 @@ def _grad_scale(M, prec):
     return float(2.0 ** int(math.floor(math.log2(max(int(M), 1))))) if prec in ("f16", "x2") else 1.0
 
 
-def _wgrad(dy, x, prec, out=None):
-    """dW = dY^T X (mm_gemm_wgrad).  An fp16 dY is the f16 networks' pre-scaled input gradient."""
+def _wgrad(dy, x, prec, out=None, nk=None):
+    """dW = dY^T X (mm_gemm_wgrad).  An fp16 dY is the f16 networks' pre-scaled input gradient; dY and X as
+    x2 planes (X2_PLANES; dY pre-scaled): nk = (N, K)."""
     from . import x3
 
     s = _grad_scale(dy.shape[0], prec)
+    if x3.is_planes(dy):
+        return x3.wgrad(dy, x, prec=prec, dscale=1.0, cscale=1.0 / s, out=out, nk=nk)
     if dy.dtype == torch.float16:
         return x3.wgrad(dy.contiguous(), x, prec=prec, dscale=1.0, cscale=1.0 / s, out=out)
     return x3.wgrad(dy.contiguous(), x, prec=prec, dscale=s, out=out)
@@ -232,6 +235,56 @@ def _wgrad(dy, x, prec, out=None):
 F16_ACT = os.environ.get("MARLMAZE_F16_ACT", "1") != "0"
 # ... and the front-end output h0 with them (MARLMAZE_F16_H0=0: fp32 h0)
 F16_H0 = os.environ.get("MARLMAZE_F16_H0", "1") != "0"
+
+
+# x2 networks: the update's hidden activations and the input gradients between the hidden layers are stored
+# as x2 planes (x3.planes: fp16 [M, width / 4, 2, 4], the (hi, lo) split every x2 kernel would apply to the fp32
+# value anyway -- the same bytes and addresses, the same MFMA operands, no repeated split, and a weight-gradient
+# kernel with nothing to convert).  The input gradients are stored pre-scaled by _grad_scale, as the f16 networks' are.  Results
+# are bit-identical to fp32 storage.  MARLMAZE_X2_PLANES=0 keeps fp32 storage (A/B runs).
+X2_PLANES = os.environ.get("MARLMAZE_X2_PLANES", "1") != "0"
+
+
+class _SavedPlanes(torch.Tensor):
+    """A plane tensor as Actor.train_forward hands it out in its saved state.  Callers look at the saved
+    activations as fp32 [M, n] matrices (the ReLU-pattern checks take ``h > 0`` of each), so to every torch
+    operation and property (shape, dtype, comparisons, arithmetic) this object IS the fp32 [M, n] matrix of the
+    values it stands for (hi + 2^-11 lo), computed on demand.  The one way to the storage is ``planes()``: the
+    fp16 [M, n / 4, 2, 4] plane tensor, which train_backward takes."""
+
+    _STORAGE = ("as_subclass",)  # planes() itself
+
+    @staticmethod
+    def __new__(cls, p):
+        return torch.Tensor._make_subclass(cls, p)
+
+    def planes(self):
+        return self.as_subclass(torch.Tensor)
+
+    def values(self):
+        p = self.planes()
+        return (p[:, :, 0, :].float() + p[:, :, 1, :].float() * (1.0 / 2048.0)).reshape(p.shape[0], -1)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if getattr(func, "__name__", "") in cls._STORAGE:
+            with torch._C.DisableTorchFunctionSubclass():
+                return func(*args, **kwargs)
+        from torch.utils._pytree import tree_map
+
+        def val(a):
+            return a.values() if isinstance(a, _SavedPlanes) else a
+
+        return func(*tree_map(val, args), **tree_map(val, kwargs))
+
+
+def _x2p(prec, M, shapes):
+    """Plane storage of the activations between the layers ``shapes`` [(N, K), ...] reads: x2, and every one
+    of those layers takes planes at M rows (forward, input gradient and weight gradient)."""
+    from . import x3
+
+    return X2_PLANES and prec == "x2" and M > 0 and all(x3.x2p_ok(M, n, k) for n, k in shapes)
 
 
 def _act16(prec, M, widths, next_ks):
@@ -257,24 +310,27 @@ def _trunk_max_rows(prec):
     return TRUNK_MAX_ROWS if TRUNK_MAX_ROWS is not None else _TRUNK_MAX_ROWS_DEFAULT.get(prec, 0)
 
 
-def _mlp_fwd(h0, ws, bs, prec, need_bits, act16=False):
+def _mlp_fwd(h0, ws, bs, prec, need_bits, act16=False, x2p=False):
     """The ReLU layers on the engine; returns the activations [h0, h1, ...] and
     the forward GEMMs' ReLU bit masks (None without need_bits).  act16: the
-    layers' outputs in fp16 (f16 with bits only, see F16_ACT).  Three layers
+    layers' outputs in fp16 (f16 with bits only, see F16_ACT).  x2p: the outputs
+    of all layers but the last as x2 planes (x2 with bits, see X2_PLANES).  Three layers
     without bits at <= _trunk_max_rows(prec) rows: one fused launch, and only h0
     and the last layer's output are returned ([h0, None, None, h3])."""
     from . import x3
 
     M, dev = h0.shape[0], h0.device
-    if not need_bits and not act16 and len(ws) == 3 and 0 < M <= _trunk_max_rows(prec) and h0.dtype == torch.float32:
+    if not need_bits and not act16 and not x2p and len(ws) == 3 and 0 < M <= _trunk_max_rows(prec) and h0.dtype == torch.float32:
         packs = [x3.pack(w, prec=prec) for w in ws]
         if x3.trunk3_ok(M, h0, packs, prec):
             return [h0, None, None, x3.trunk3(h0, packs, bs)], [None, None, None]
     hs, bits = [h0], []
     h = h0
-    for w, b in zip(ws, bs):
+    for l, (w, b) in enumerate(zip(ws, bs)):
         mb = x3.mbits(M, dev) if need_bits else None
         out = torch.empty((M, w.shape[0]), dtype=torch.float16, device=dev) if act16 else None
+        if x2p and l + 1 < len(ws):
+            out = x3.planes(M, w.shape[0], dev)
         h = x3.gemm(h, x3.pack(w, prec=prec), bias=b, relu=True, mbits_out=mb, out=out)
         hs.append(h)
         bits.append(mb)
@@ -286,19 +342,21 @@ def _mlp_bwd(ctx_bits, hs, ws, dy, cs, prec, need_dx, outs=None):
     its ReLU) and that dY's per-tile column sums cs (None: sum dY itself).
     outs: destinations [dW0, db0, dW1, db1, ...] (or None: allocated).
     An fp16 dY is the f16 networks' pre-scaled input gradient (fp16(dY s), see
-    _g16): the layers' input gradients then stay fp16 pre-scaled too.
+    _g16): the layers' input gradients then stay fp16 pre-scaled too.  A dY as
+    x2 planes (pre-scaled, X2_PLANES) goes with hs[l] as planes; the gradient
+    into a layer whose input is stored fp32 (h0) is fp32 again.
     Returns (dx or None, [dW0, db0, dW1, db1, ...])."""
     from . import x3
 
     L = len(ws)
     M = dy.shape[0]
     s = _grad_scale(M, prec)
-    g16 = dy.dtype == torch.float16
     grads = [None] * (2 * L)
     dx = None
     for l in range(L - 1, -1, -1):
+        g16 = dy.dtype == torch.float16  # fp16 or planes: pre-scaled
         o_w, o_b = (outs[2 * l], outs[2 * l + 1]) if outs is not None else (None, None)
-        grads[2 * l] = _wgrad(dy, hs[l], prec, out=o_w)
+        grads[2 * l] = _wgrad(dy, hs[l], prec, out=o_w, nk=tuple(ws[l].shape))
         assert cs is not None or not g16, "an fp16 dY comes with its column sums"
         grads[2 * l + 1] = x3.colsum(dy if cs is None else cs, out=o_b)
         wt = x3.pack(ws[l], trans=True, prec=prec)
@@ -307,6 +365,8 @@ def _mlp_bwd(ctx_bits, hs, ws, dy, cs, prec, need_dx, outs=None):
         if l > 0:  # dY of layer l-1 = (dY W) * (h_l > 0): the ReLU bits of layer l-1's forward
             cs = x3.colsum_buf(M, ws[l].shape[1], dy.device)
             out = torch.empty((M, ws[l].shape[1]), dtype=torch.float16, device=dy.device) if g16 else None
+            if x3.is_planes(dy):  # planes again where the layer below stores its input as planes
+                out = x3.planes(M, ws[l].shape[1], dy.device) if x3.is_planes(hs[l - 1]) else None
             dy = x3.gemm(dy, wt, mbits_in=ctx_bits[l - 1], colsum=cs, ascale=ascale, cscale=cscale, out=out,
                          oscale=s)
         elif need_dx:
@@ -351,14 +411,14 @@ def _heads_fwd(h, wh, bh):
     return out
 
 
-def _heads_bwd(dz, h, wh, bits, out_w=None, out_b=None, oscale=None):
+def _heads_bwd(dz, h, wh, bits, out_w=None, out_b=None, oscale=None, x2p=False):
     """The heads' backward: (dY through the last ReLU, its tile column sums, dWh, dbh).  oscale: dY
-    stored fp16 pre-scaled (fp16(dY oscale), see _g16)."""
+    stored fp16 pre-scaled (fp16(dY oscale), see _g16), or with x2p as x2 planes of dY oscale."""
     from . import x3
 
     dwh = _wgrad(dz, h, "x3", out=out_w)
     dbh = x3.colsum(dz, out=out_b)
-    dy, cs = x3.heads_bwd(dz, wh, bits, oscale=oscale)  # (dz Wh) * (h > 0)
+    dy, cs = x3.heads_bwd(dz, wh, bits, oscale=oscale, x2p=x2p)  # (dz Wh) * (h > 0)
     return dy, cs, dwh, dbh
 
 
@@ -630,23 +690,34 @@ class Actor(nn.Module):
         ws, h0 = _front_fwd(x, self.projection.parity_mode, front_params(self.projection, self.attention), h16=h16)
         if not self._engine(h0):
             raise ValueError("Actor.train_forward needs the GPU engine's shapes (ReLU, widths <= 272)")
-        hs, bits = _mlp_fwd(h0, params[0::2], params[1::2], self.gemm_prec, True, act16=act16)
+        # x2: h1 .. h_{L-1} as x2 planes (h0 and the last layer's output, which the heads read, stay fp32)
+        x2p = len(wl) > 1 and _x2p(self.gemm_prec, x.shape[0], [tuple(w_.shape) for w_ in wl[1:]])
+        hs, bits = _mlp_fwd(h0, params[0::2], params[1::2], self.gemm_prec, True, act16=act16, x2p=x2p)
         w, b = self.heads()
         z = _heads_fwd(hs[-1], w, b)
+        if x2p:  # (a caller computing with a saved plane tensor sees its fp32 values)
+            from . import x3
+
+            hs = [_SavedPlanes(h) if x3.is_planes(h) else h for h in hs]
         return z, (x, ws, hs, bits)
 
     def train_backward(self, saved, dz):
         """Every parameter's gradient for d loss / d z (dz [M, 6]), written into
         the parameters' .grad storage (allocated when absent)."""
         x, ws, hs, bits = saved
+        hs = [h.planes() if isinstance(h, _SavedPlanes) else h for h in hs]
         L = len(self.layers)
         w, _ = self.heads()
         gw = self._adjacent(_grad_of(self.move_head.weight), _grad_of(self.mark_head.weight))
         gb = self._adjacent(_grad_of(self.move_head.bias), _grad_of(self.mark_head.bias))
         params = self._mlp_params()
         g16 = _g16(self.gemm_prec, hs, params[0::2], True)
+        from . import x3
+
+        x2p = x3.is_planes(hs[L - 1])  # the last layer's input as planes: its dY as (pre-scaled) planes too
         dy, cs, dwh, dbh = _heads_bwd(dz.contiguous(), hs[L], w, bits[L - 1], out_w=gw, out_b=gb,
-                                      oscale=_grad_scale(dz.shape[0], self.gemm_prec) if g16 else None)
+                                      oscale=_grad_scale(dz.shape[0], self.gemm_prec) if g16 or x2p else None,
+                                      x2p=x2p)
         if gw is None:
             self.move_head.weight.grad.copy_(dwh[:5])
             self.mark_head.weight.grad.copy_(dwh[5:])

@@ -209,6 +209,26 @@ def gemm(a, b, bias=None, relu=False, mbits_in=None, mbits_out=None, colsum=None
             res = gemm(a, pack(src, trans=trans, prec="x3"), bias, relu, mbits_in, mbits_out, colsum, 1.0, out)
         return res
     N, K = b.R, b.C
+    if is_planes(a) or (out is not None and is_planes(out)):  # x2 plane storage (mm_gemm_nt_h's _X2P flags)
+        assert b.prec == "x2", b.prec
+        M = a.shape[0]
+        flags = 0
+        if is_planes(a):
+            assert _plane_rows(a) and a.shape[1] == K // 4 and float(ascale) == 1.0, (a.shape, K, ascale)
+            flags |= _lib.GEMM_A_X2P
+        else:
+            assert a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == K, (a.shape, K)
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+        if is_planes(out):
+            assert _plane_rows(out) and out.shape[:2] == (M, N // 4) and N % 4 == 0, (out.shape, M, N)
+            flags |= _lib.GEMM_C_X2P
+        cs = 1.0 / float(ascale) if cscale is None else float(cscale)
+        _lib.check(_lib.lib().mm_gemm_nt_h(PRECS[b.prec], flags, _lib.ptr(a), _pitch(a), float(ascale), b.ptr(),
+                                           M, N, K, _lib.ptr(bias), int(relu), _lib.ptr(mbits_in),
+                                           _lib.ptr(mbits_out), _lib.ptr(colsum), cs, float(oscale), _lib.ptr(out),
+                                           _pitch(out), _lib.stream_ptr()), "mm_gemm_nt_h")
+        return out
     assert a.dtype in (torch.float32, torch.float16) and a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == K, \
         (a.dtype, a.shape, K)
     M = a.shape[0]
@@ -284,6 +304,34 @@ def trunk3_head_sample(h0, packs, biases, head_w, head_b, masks, seed, offset, a
     return actions, logp, joint_logp
 
 
+def planes(M, n, device):
+    """Storage for the x2 planes of an [M, n] activation or input gradient (n % 4 == 0): fp16 [M, n / 4, 2, 4],
+    per row and group of four columns the four hi halves, then the four lo halves (hi = fp16(x s), lo =
+    fp16(2^11 (x s - hi))) -- the bytes and addresses of the fp32 matrix.  A view of the leading column groups
+    of a wider plane tensor is a plane tensor too (a row pitch, as an fp32 matrix's)."""
+    assert int(n) % 4 == 0, n
+    return torch.empty((int(M), int(n) // 4, 2, 4), dtype=torch.float16, device=device)
+
+
+def is_planes(t):
+    return t is not None and t.dim() == 4 and t.dtype == torch.float16 and t.shape[2:] == (2, 4)
+
+
+def _plane_rows(t):
+    return t.stride()[1:] == (8, 4, 1) and t.stride(0) % 8 == 0
+
+
+def _pitch(t):
+    """The leading dimension the library takes: the row pitch in 4-byte units (fp32 elements or plane pairs)."""
+    return t.stride(0) // 2 if is_planes(t) else t.stride(0)
+
+
+def x2p_ok(M, N, K):
+    """Whether the x2 layer [M, K] -> [M, N] takes plane storage end to end (mm_gemm_x2p_ok: the weight
+    gradient [N, K] has the plane kernel's blocks)."""
+    return bool(_lib.lib().mm_gemm_x2p_ok(int(M), int(N), int(K)))
+
+
 def a16_ok(M, N, K):
     """Whether an f16 GEMM of that shape takes fp16 A (mm_gemm_a16_ok: the B-resident kernel's shapes)."""
     return bool(_lib.lib().mm_gemm_a16_ok(int(M), int(N), int(K), int(K), int(N)))
@@ -318,13 +366,21 @@ def set_wgrad_algo(name):
     return {v: k for k, v in WGRAD_ALGO.items()}[prev]
 
 
-def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None):
+def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None, nk=None):
     """dW [N, K] = dY^T X summed over the M rows (mm_gemm_wgrad), dY [M, N] and
     X [M, K] fp32 row-major; fp16 operands take dY * dscale (a power of two).
     Inside a ``deferred()`` scope with ``out`` given, the row-slice partials'
     sum runs when the scope ends.  checked (x2 / f16): as gemm()'s -- redone at
-    x3 when an operand left the fp16 range."""
-    if checked and prec != "x3":
+    x3 when an operand left the fp16 range.  dY and X both as x2 planes (planes(); prec x2, dscale 1, cscale the
+    inverse of dY's scale): nk = (N, K), the logical widths."""
+    if is_planes(dy) or is_planes(x):
+        assert is_planes(dy) and is_planes(x) and prec == "x2" and not checked and float(dscale) == 1.0
+        N, K = nk
+        M = dy.shape[0]
+        assert x.shape[0] == M and _plane_rows(dy) and _plane_rows(x)
+        assert dy.shape[1] == N // 4 and x.shape[1] == K // 4, (dy.shape, x.shape, nk)
+        flags = _lib.GEMM_A_X2P | _lib.GEMM_B_X2P
+    elif checked and prec != "x3":
         if dy.dtype == torch.float16 or x.dtype == torch.float16 or cscale is not None:
             # the x3 redo reads fp32 operands and has no output scale: a pre-scaled fp16 dY would come back
             # scaled by its s
@@ -334,13 +390,15 @@ def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None):
         if int(range_flag(clear=True).item()):
             res = wgrad(dy, x, "x3", 1.0, out)
         return res
-    M, N = dy.shape
-    K = x.shape[1]
-    assert x.shape[0] == M and dy.stride(1) == 1 and x.stride(1) == 1
-    assert x.dtype in (torch.float32, torch.float16) and dy.dtype in (torch.float32, torch.float16), (x.dtype, dy.dtype)
-    # fp16 X: f16 activations (x3 / f16); fp16 dY: f16's pre-scaled input gradients (dscale 1, cscale the inverse)
-    flags = ((_lib.GEMM_B_F16 if x.dtype == torch.float16 else 0)
-             | (_lib.GEMM_A_F16 if dy.dtype == torch.float16 else 0))
+    else:
+        M, N = dy.shape
+        K = x.shape[1]
+        assert x.shape[0] == M and dy.stride(1) == 1 and x.stride(1) == 1
+        assert x.dtype in (torch.float32, torch.float16) and dy.dtype in (torch.float32, torch.float16), \
+            (x.dtype, dy.dtype)
+        # fp16 X: f16 activations (x3 / f16); fp16 dY: f16's pre-scaled input gradients (dscale 1, cscale the inverse)
+        flags = ((_lib.GEMM_B_F16 if x.dtype == torch.float16 else 0)
+                 | (_lib.GEMM_A_F16 if dy.dtype == torch.float16 else 0))
     cs = 1.0 / float(dscale) if cscale is None else float(cscale)
     defer = bool(_DEFER) and out is not None and M > 0  # a result the caller reads now is never deferred
     if out is None:
@@ -351,7 +409,7 @@ def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None):
         S = L.mm_gemm_wgrad_slices(PRECS[prec], M, N, K)
         _lib.check(S if S < 0 else 0, "mm_gemm_wgrad_slices")
         ws = torch.empty(S * N * K, dtype=torch.float32, device=dy.device)
-        args = (_lib.ptr(dy), dy.stride(0), float(dscale), _lib.ptr(x), x.stride(0), M, N, K, cs,
+        args = (_lib.ptr(dy), _pitch(dy), float(dscale), _lib.ptr(x), _pitch(x), M, N, K, cs,
                 _lib.ptr(ws), _lib.stream_ptr())
         _lib.check(L.mm_gemm_wgrad_partials_h(PRECS[prec], flags, *args) if flags
                    else L.mm_gemm_wgrad_partials(PRECS[prec], *args), "mm_gemm_wgrad_partials")
@@ -360,7 +418,7 @@ def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None):
         d.keep += [ws, out]
         return out
     ws = torch.empty(max(1, L.mm_gemm_wgrad_ws_len(M, N, K)), dtype=torch.float32, device=dy.device)
-    args = (_lib.ptr(dy), dy.stride(0), float(dscale), _lib.ptr(x), x.stride(0), M, N, K, cs,
+    args = (_lib.ptr(dy), _pitch(dy), float(dscale), _lib.ptr(x), _pitch(x), M, N, K, cs,
             _lib.ptr(ws), _lib.ptr(out), _lib.stream_ptr())
     _lib.check(L.mm_gemm_wgrad_h(PRECS[prec], flags, *args) if flags else L.mm_gemm_wgrad(PRECS[prec], *args),
                "mm_gemm_wgrad")
@@ -432,13 +490,19 @@ def colsum(x, out=None, slabs=256):
     return out
 
 
-def heads_bwd(dz, w, bits, oscale=None):
+def heads_bwd(dz, w, bits, oscale=None, x2p=False):
     """dY = (dz [M, J] @ w [J, N]) * bits, and its per-tile column sums.  oscale: dY stored fp16 as
-    fp16(dY * oscale) (the f16 networks' pre-scaled input gradients, mm_x3_heads_bwd_h16)."""
+    fp16(dY * oscale) (the f16 networks' pre-scaled input gradients, mm_x3_heads_bwd_h16), or with x2p as
+    the x2 planes of dY * oscale (planes(), mm_x3_heads_bwd_x2p)."""
     M, J = dz.shape
     N = w.shape[1]
     dz, w = dz.contiguous(), w.contiguous()
     cs = colsum_buf(M, N, dz.device)
+    if x2p:
+        dy = planes(M, N, dz.device)
+        _lib.check(_lib.lib().mm_x3_heads_bwd_x2p(_lib.ptr(dz), J, _lib.ptr(w), _lib.ptr(bits), M, N, _lib.ptr(dy),
+                                                  _lib.ptr(cs), float(oscale), _lib.stream_ptr()), "mm_x3_heads_bwd_x2p")
+        return dy, cs
     if oscale is not None:
         dy = torch.empty((M, N), dtype=torch.float16, device=dz.device)
         _lib.check(_lib.lib().mm_x3_heads_bwd_h16(_lib.ptr(dz), J, _lib.ptr(w), _lib.ptr(bits), M, N, _lib.ptr(dy),
