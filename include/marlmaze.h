@@ -667,6 +667,27 @@ int mm_elog_step(const mm_env_t* env, const int8_t* actions, const uint8_t* done
 int mm_critic_value(const float* x, int ldx, int K0, int M, int H0, int H1, const float* w0, const float* b0,
                     const float* w1, const float* b1, const float* w2, const float* b2, float* v, void* stream);
 
+/* The per-row part of the update's critic in one launch (MM_PREC_X2; PPO.py:78-80 with networks.py:96-102):
+ * for x [M, K0] (row stride ldx, 8-byte aligned rows) and rtg [M] it writes what three forward mm_gemm_nt
+ * calls, mm_mse_loss, mm_x3_heads_bwd (J = 1) and the input-gradient mm_gemm_nt would, bit for bit:
+ *   v [M] the values and dv [M] = (v - rtg) 2 / M;
+ *   h0, h1 [M, 64] the hidden activations; dy1 = dv w2 (h1 > 0) and dy0 = (dy1 W1) (h0 > 0), fp32 [M, 64],
+ *   the latter's operands scaled by 2^floor(log2 M) on two fp16 planes (a non-finite accumulator raises the
+ *   range flag, mm_gemm_range_flag);
+ *   cs1, cs0 [ceil(M / 16), 64] the column sums of dy1 / dy0 per 16-row tile (mm_colsum's input).
+ * The weight gradients then come from mm_gemm_wgrad on (dv, h1), (dy1, h0), (dy0, x) as before.
+ * w0_tp, w1_tp, w1t_tp, w2_tp: the MM_PREC_X2 TP packs (mm_gemm_tp_pack) of W0 [64, K0], W1 [64, 64], W1
+ * transposed, and w2 [1, 64]; w2: the fp32 row itself.
+ * mm_critic_update_ok: 1 for the shapes served -- K0 = 130 or 132 (the critic of two agents), ldx even, and M
+ * rows for which every GEMM of the separate launches runs on the B-resident kernel (MARLMAZE_BRES_MIN_ROWS,
+ * 16,384 by default: that kernel's bits are the ones reproduced); elsewhere mm_critic_update returns MM_E_ARG
+ * and the caller runs the separate launches. */
+int mm_critic_update_ok(int M, int K0, int ldx);
+int mm_critic_update(const float* x, int ldx, int K0, int M, const float* rtg, const uint16_t* w0_tp, const float* b0,
+                     const uint16_t* w1_tp, const uint16_t* w1t_tp, const float* b1, const uint16_t* w2_tp,
+                     const float* w2, const float* b2, float* v, float* dv, float* h0, float* h1, float* dy1,
+                     float* dy0, float* cs1, float* cs0, void* stream);
+
 /* Actor front-end, fused (networks.py:31-34,51-82): the 23 feature embeddings
  * (Projection; parity != 0 keeps quirk Q1, every embedding reads x[:, 0:d_i]),
  * Q/K/V, softmax(QK^T/sqrt(10))V and the residual.

@@ -279,10 +279,14 @@ class PPO:
             # backward's bias-gradient and weight-gradient reductions together at its end
             x3.pack_many(self.critic.pack_specs() + self.actor.pack_specs())
             with _lib.on_side(_lib.side_stream("critic", obs.device) if beside else None) as critic_side:
-                V, csaved = self.critic.train_forward(obs.reshape(M, -1))
-                mse_part, dv = update.mse_loss(V, rtg)
-                with x3.deferred():
-                    self.critic.train_backward(csaved, dv)
+                xc = obs.reshape(M, -1)
+                if self.critic.fused_update_ok(xc):  # (x2, the reference widths, M >= the B-resident threshold)
+                    _, mse_part = self.critic.train_update_fused(xc, rtg)
+                else:
+                    V, csaved = self.critic.train_forward(xc)
+                    mse_part, dv = update.mse_loss(V, rtg)
+                    with x3.deferred():
+                        self.critic.train_backward(csaved, dv)
             heads, asaved = self.actor.train_forward(obs.reshape(2 * M, 65))
             coef, ppo_part = _ppo_loss_fwd(heads, mk, a8, old_logp, adv, self.clip)
             dz = _ppo_loss_bwd(heads, mk, a8, coef, self._one)

@@ -244,6 +244,11 @@ F16_H0 = os.environ.get("MARLMAZE_F16_H0", "1") != "0"
 # are bit-identical to fp32 storage.  MARLMAZE_X2_PLANES=0 keeps fp32 storage (A/B runs).
 X2_PLANES = os.environ.get("MARLMAZE_X2_PLANES", "1") != "0"
 
+# x2 critic: the update's three forward GEMMs, dV, the head's backward and the input-gradient GEMM as one launch
+# (mm_critic_update, Critic.train_update_fused) from the B-resident GEMM's row threshold upwards; every value
+# is the separate launches' bit for bit.  MARLMAZE_CRITIC_FUSED=0 keeps the separate launches (A/B runs).
+CRITIC_FUSED = os.environ.get("MARLMAZE_CRITIC_FUSED", "1") != "0"
+
 
 class _SavedPlanes(torch.Tensor):
     """A plane tensor as Actor.train_forward hands it out in its saved state.  Callers look at the saved
@@ -873,6 +878,60 @@ class Critic(nn.Module):
         assert x.is_cuda and self._engine(x)
         v, hs, bits = _critic_fwd(x, self._params(), self.gemm_prec, True)
         return v, (hs, bits)
+
+    def fused_update_ok(self, x):
+        """Whether train_update_fused serves x [M, agents * 65]: CRITIC_FUSED, the x2 arithmetic, the reference
+        critic's widths (64 / 64 hidden, 130 inputs: two agents), unit-stride rows, and M from the
+        B-resident GEMM's row threshold upwards (mm_critic_update_ok: the fused forward gives that kernel's
+        bits, which the streaming kernel below the threshold is not guaranteed to share)."""
+        from . import _lib
+
+        if not (CRITIC_FUSED and self.gemm_prec == "x2" and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 2 and x.stride(1) == 1 and len(self.layers) == 3 and self.activation is nn.ReLU):
+            return False
+        w0, w1, w2 = (lin.weight for lin in self.layers)
+        if not (w0.shape == (64, x.shape[1]) and w1.shape == (64, 64) and w2.shape == (1, 64)):
+            return False
+        return _lib.lib().mm_critic_update_ok(x.shape[0], x.shape[1], x.stride(0)) == 1
+
+    def train_update_fused(self, x, rtg, grads=None):
+        """Forward, nn.MSELoss()(V, rtg) and every parameter's gradient of it (fused_update_ok(x) shapes): the
+        per-row work -- the three layers, dV, dY1 and dY0 with their 16-row column sums -- in one launch
+        (mm_critic_update), then train_backward's weight-gradient and column-sum launches on its outputs.
+        Every value is the separate launches' bit for bit.  x [M, agents * 65], rtg [M]; grads: the six
+        destinations in parameter order (default: the parameters' .grad).  Returns (V [M, 1], the loss's partial
+        sums for update.losses_final)."""
+        from . import _lib, update, x3
+
+        assert self.fused_update_ok(x), "train_update_fused: see fused_update_ok"
+        L = _lib.lib()
+        M, K0 = x.shape
+        dev = x.device
+        params = self._params()
+        w0, b0, w1, b1, w2, b2 = params
+        o = grads if grads is not None else [_grad_of(p) for p in params]
+        rtg = rtg.reshape(M).contiguous()
+        assert rtg.dtype == torch.float32 and rtg.is_cuda
+        prec = self.gemm_prec
+        p0, p1, p1t, p2 = (x3.pack(w0, prec=prec), x3.pack(w1, prec=prec), x3.pack(w1, trans=True, prec=prec),
+                           x3.pack(w2, prec=prec))
+        v = torch.empty((M, 1), dtype=torch.float32, device=dev)
+        dv = torch.empty((M, 1), dtype=torch.float32, device=dev)
+        h0, h1, dy1, dy0 = (torch.empty((M, 64), dtype=torch.float32, device=dev) for _ in range(4))
+        cs1, cs0 = x3.colsum_buf(M, 64, dev), x3.colsum_buf(M, 64, dev)
+        _lib.check(L.mm_critic_update(_lib.ptr(x), x.stride(0), K0, M, _lib.ptr(rtg), p0.ptr(), _lib.ptr(b0), p1.ptr(),
+                                      p1t.ptr(), _lib.ptr(b1), p2.ptr(), _lib.ptr(w2), _lib.ptr(b2),
+                                      *(_lib.ptr(t) for t in (v, dv, h0, h1, dy1, dy0, cs1, cs0)),
+                                      _lib.stream_ptr()), "mm_critic_update")
+        part, _ = update.mse_loss(v, rtg, dv=False)  # the loss's partial sums (dV is the kernel's)
+        with x3.deferred():  # _critic_bwd's reductions, in its order
+            _wgrad(dv, h1, prec, out=o[4])
+            x3.colsum(dv, out=o[5])
+            _wgrad(dy1, h0, prec, out=o[2], nk=tuple(w1.shape))
+            x3.colsum(cs1, out=o[3])
+            _wgrad(dy0, x.contiguous(), prec, out=o[0], nk=tuple(w0.shape))
+            x3.colsum(cs0, out=o[1])
+        return v, part
 
     def pack_specs(self):
         """The weight packs (x3.pack_many specs) of one train_forward + train_backward."""

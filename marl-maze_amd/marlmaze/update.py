@@ -224,11 +224,14 @@ def _workspace(dev, n):
 
 
 def mse_loss(v, rtg, dv=None):
-    """nn.MSELoss()(V, rtg) partial sums and its gradient (mm_mse_loss).  Returns (partials, dv)."""
+    """nn.MSELoss()(V, rtg) partial sums and its gradient (mm_mse_loss).  Returns (partials, dv); dv=False:
+    the partial sums only (None for dv)."""
     L = _lib.lib()
     M = v.numel()
     v, rtg = v.reshape(M).contiguous(), rtg.reshape(M).contiguous()
-    if dv is None:
+    if dv is False:
+        dv = None
+    elif dv is None:
         dv = torch.empty(M, dtype=torch.float32, device=v.device)
     part = torch.empty(L.mm_mse_loss_partials(M), dtype=torch.float32, device=v.device)
     _lib.check(L.mm_mse_loss(_lib.ptr(v), _lib.ptr(rtg), M, _lib.ptr(dv), _lib.ptr(part), _lib.stream_ptr()),
