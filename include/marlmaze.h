@@ -373,17 +373,28 @@ int mm_heads_fwd_h16(const void* h, int ldh, int K, const float* w, const float*
  * operands, no repeated split; results are bit-identical to fp32 storage.
  * Replaces nothing in the reference (its networks are fp32, networks.py:31-41).
  * mm_gemm_nt_h with MM_GEMM_A_X2P: a is such a plane tensor (ascale 1; with
- *   mbits_in or mbits_out only: the hidden layers' forms);
+ *   mbits_in or mbits_out: the hidden layers' forms; without either, the
+ *   plain input gradient into an fp32-stored layer input, on the B-resident
+ *   kernel only -- below its row threshold, under MM_GEMM_STREAM or past one
+ *   row chunk MM_E_ARG; mm_gemm_x2p_dy_ok says whether the shape takes it);
  *   MM_GEMM_C_X2P: c likewise (N % 4 == 0), the forward with mbits_out or the
  *   input gradient with mbits_in (planes of out * oscale).
  * mm_gemm_wgrad_h / _partials_h with MM_GEMM_A_X2P | MM_GEMM_B_X2P: dy and x
  *   both plane tensors (dscale 1), at the shapes mm_gemm_x2p_ok accepts
  *   (the 264 x 264 layers' blocks); other shapes are MM_E_ARG.
+ *   With MM_GEMM_A_X2P alone: dy a plane tensor (dscale 1), x fp32 (rows
+ *   16-byte aligned), at the 264 x 460 layer's blocks (17 x 8); the partials
+ *   are those of the fp32 dy at dscale s, bit for bit.
+ * mm_gemm_x2p_dy_ok: nonzero when the input gradient dY [M, N] of the layer
+ *   [M, K] -> [M, N] can be stored as planes beside an fp32 layer input: both
+ *   the mixed weight gradient [N, K] and the plain plane-A input gradient of
+ *   width K run at M rows under the current mm_gemm_nt_algo setting.
  * mm_x3_heads_bwd_x2p: mm_x3_heads_bwd writing dy as planes of dY * oscale. */
 #define MM_GEMM_A_X2P 8
 #define MM_GEMM_C_X2P 16
 #define MM_GEMM_B_X2P 32
 int mm_gemm_x2p_ok(int M, int N, int K);
+int mm_gemm_x2p_dy_ok(int M, int N, int K);
 int mm_x3_heads_bwd_x2p(const float* dz, int J, const float* W, const uint32_t* bits, int M, int N, void* dy,
                         float* colsum, float oscale, void* stream);
 /* mm_actor_front_fwd with h stored fp16 [B, 460] (round to nearest of the fp32

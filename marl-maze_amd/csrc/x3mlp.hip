@@ -2395,6 +2395,331 @@ __global__ __launch_bounds__(kWgThreads) void k_wgrad_tr(const uint32_t* __restr
     range_note<P>(rm);
 }
 
+// k_wgrad_mix: k_wgrad_dma for dY stored as pre-scaled x2 planes beside an fp32 X (the first trunk layer:
+// dW1 = dY1^T h0, 264 x 460, where h0 has no plane form).  k_wgrad_dma's plan, tile runs and MFMA order per
+// output tile; the dY side is k_wgrad_tr's (plane rows by LDS-DMA at pitch tr_pitch(TN), A fragments straight
+// from the raw stage with ds_read_b64_tr_b16: nothing converted, no image part -- under k_wgrad_dma every one
+// of the ncb column blocks converted the whole dY step again), the X side k_wgrad_dma's (raw fp32 rows by
+// LDS-DMA, store_piece_x2_plain<false> into an image of NTK tiles).  The fragments are the ones k_wgrad_dma's
+// image holds (see k_wgrad_tr), so the partials are its partials, bit for bit.
+//
+// LDS: two dY stages (32 rows of pitch wpA pieces) and two raw X stages (32 rows x 16 NTK floats), 2 x (34,816
+// + 16,384) bytes at <17, 8>, and the X images.  Two forms ("dY1 as planes"; measured
+// 419,430 rows: 366-386 us for the second against 395-417 for the first and 460-481 for k_wgrad_dma):
+// WG_MIX_OVERLAP=0: one image (118,784 bytes).  Per step: the wave's A fragments from the step's stage; a
+// barrier (every wave holds its fragments: the stage, whose X part the step before converted, is free); the DMA
+// of the step after next into it, so that two steps' bytes are in flight under the MFMAs, which read B from the
+// image; the counted wait for this wave's DMAs of the next step; a barrier; the next step's X conversion; a
+// barrier.  WG_MIX_OVERLAP=1 (the default): two images (135,168 bytes), the next step's X converted between
+// this step's MFMAs, one barrier per step (see there).  A column block's k-tiles wholly past K (the last
+// block's three at K = 460; WG_MIX_NO_SKIP: a diagnostic build without the skip, 402 us) are skipped: they are
+// never stored.  Operand rule as k_wgrad_dma's: one offset set per stage, advanced in place by two steps after
+// its previous DMA was waited for; the resource SGPRs held for the whole kernel.  The range guard runs over
+// the stored accumulators only (columns past N / K may hold anything, NaN patterns of a pitch padding
+// included).
+#ifndef WG_MIX_OVERLAP
+#define WG_MIX_OVERLAP 1
+#endif
+template <int TN, int NTK>
+__global__ __launch_bounds__(kWgThreads) void k_wgrad_mix(const uint32_t* __restrict__ dy, int lddy,
+                                                          const float* __restrict__ x, int ldx, int M, int N, int K,
+                                                          int rows, int nslices, int ncb, float cscale,
+                                                          float* __restrict__ ws) {
+    constexpr int P = P_X2;
+    constexpr int kB = Prec<P>::kBlk;
+    constexpr int RN = TN / kWgWaves;
+    constexpr int kRem = (TN - kWgWaves * RN) * NTK;
+    constexpr int EX = (kRem + kWgWaves - 1) / kWgWaves;
+    static_assert(RN > 0 && (kRem == 0 || TN - kWgWaves * RN == 1), "leftover tiles of one n-tile (one A fragment)");
+    constexpr int wpA = tr_pitch(TN);                    // dY row pitch, pieces
+    constexpr int kWB = 16 * NTK;                        // X raw row width (floats)
+    constexpr int kSecA = 32 * wpA, kSecB = 32 * kWB / 4;  // an operand's part of a stage, pieces
+    static_assert(kSecA % 64 == 0 && kSecB % 64 == 0, "parts of whole DMA instructions");
+    constexpr int kInsA = kSecA / 64, kInsB = kSecB / 64;  // DMA instructions per part
+    constexpr int kImg = NTK * kB;                         // uint16
+    constexpr bool kOverlap = WG_MIX_OVERLAP != 0;
+    constexpr int kImgs = kOverlap ? 2 : 1;
+    constexpr int itemsB = 64 * NTK;
+    constexpr int kPerB = (itemsB + kWgThreads - 1) / kWgThreads;
+    static_assert(2 * (kSecA + kSecB) * 16 + kImgs * kImg * 2 <= 160 * 1024, "LDS");
+    __shared__ __attribute__((aligned(16))) uint4 rawA[2 * kSecA];
+    __shared__ __attribute__((aligned(16))) uint4 rawB[2 * kSecB];
+    __shared__ __attribute__((aligned(16))) uint16_t img[kImgs * kImg];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int s = (slot / ncb) * 8 + xcd, cb = slot % ncb;
+    if (s >= nslices) return;  // the whole workgroup
+    const int m_begin = s * rows, nrows = min(M, m_begin + rows) - m_begin;
+    const int col0 = cb * NTK * 16;
+#ifdef WG_MIX_NO_SKIP
+    constexpr int live = NTK;
+#else
+    const int live = min(NTK, (K - col0 + 15) / 16);  // the block's k-tiles that reach a stored column
+#endif
+    __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(dy + (size_t)m_begin * lddy), (short)0, (int)(nrows * lddy * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(x + (size_t)m_begin * ldx + col0), (short)0, (int)((nrows * ldx - col0) * 4), 0x00020000);
+    asm volatile("" : "+s"(rsA));
+    asm volatile("" : "+s"(rsB));
+
+    // this wave's DMA instructions a = wave + 8 k of dY's part, b = wave + 8 k of X's (k_wgrad_tr's scheme: the
+    // operand of an offset slot is a compile-time fact); dY's unused pieces (row padding): out of range
+    constexpr int kSlotA = (kInsA + kWgWaves - 1) / kWgWaves, kSlotB = (kInsB + kWgWaves - 1) / kWgWaves;
+    uint32_t obA[2][kSlotA], obB[2][kSlotB];
+#pragma unroll
+    for (int k = 0; k < kSlotA; k++) {
+        const int e = 64 * min(wave + kWgWaves * k, kInsA - 1) + lane;  // (clamped: not issued)
+        const int r = e / wpA, c = e % wpA;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            obA[t][k] = c < 4 * TN ? (uint32_t)(((32 * t + r) * lddy + 4 * c) * 4) : kBufOOB;
+            asm volatile("" : "+v"(obA[t][k]));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kSlotB; k++) {
+        const int e = 64 * min(wave + kWgWaves * k, kInsB - 1) + lane;
+        const int r = e / (kWB / 4), c4 = e % (kWB / 4);
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            obB[t][k] = (uint32_t)(((32 * t + r) * ldx + 4 * c4) * 4);
+            asm volatile("" : "+v"(obB[t][k]));
+        }
+    }
+    const uint32_t stepA = 2u * 32u * (uint32_t)lddy * 4u, stepB = 2u * 32u * (uint32_t)ldx * 4u;
+    auto issueA = [&](auto tc, int st) {  // the DMA of step st's dY rows into dY stage T (offset set T)
+        constexpr int T = decltype(tc)::value;
+        const uint32_t base = lds_addr(rawA + T * kSecA);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < kSlotA; k++) {
+            const int a = wave + kWgWaves * k;  // wave-uniform
+            if (a < kInsA) {
+                if (st >= 2) asm volatile("v_add_u32 %0, %0, %1" : "+v"(obA[T][k]) : "s"(stepA));
+                dma16(rsA, obA[T][k], base + 1024u * (uint32_t)a);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto issueB = [&](auto tc, int st) {  // ... of its X rows into X stage T
+        constexpr int T = decltype(tc)::value;
+        const uint32_t base = lds_addr(rawB + T * kSecB);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < kSlotB; k++) {
+            const int bi = wave + kWgWaves * k;
+            if (bi < kInsB) {
+                if (st >= 2) asm volatile("v_add_u32 %0, %0, %1" : "+v"(obB[T][k]) : "s"(stepB));
+                dma16(rsB, obB[T][k], base + 1024u * (uint32_t)bi);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // instructions per wave and step: the count a wave may leave in flight (the later step's)
+    constexpr int kRemA = kInsA % kWgWaves, kRemB = kInsB % kWgWaves;
+    static_assert(kRemA != 0 && kRemB == 0, "waves below kRemA issue one more instruction (of dY)");
+    constexpr int kInsW = kSlotA + kSlotB, kInsWmin = kInsW - 1;
+    // this wave's DMAs of the step converted next have landed; only the later step's may be in flight
+    auto wait_stage = [&](bool later_in_flight) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (later_in_flight) {
+            if (wave < kRemA) {
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (kInsW & 15) | ((kInsW >> 4) << 14));
+            } else {
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (kInsWmin & 15) | ((kInsWmin >> 4) << 14));
+            }
+        } else {
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");
+    };
+    auto barrier = [&]() {  // this wave's LDS accesses done; the DMAs waited for above visible to the workgroup
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt((15 << 0) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // the X pieces of a stage -> the image (k_wgrad_dma's piece_conv of its B part)
+    auto convB = [&](const float* xs, uint16_t* im) {
+#pragma unroll
+        for (int q = 0; q < kPerB; q++) {
+            const int e = threadIdx.x + kWgThreads * q;
+            if (e < itemsB) {
+                const int c = e / kWB, j = e - c * kWB;
+                const float* src = xs + 8 * c * kWB + j;
+                float v[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) v[i] = src[i * kWB];
+                const int loff = (j >> 4) * kB + c * 128 + (j & 15) * 8;
+                store_piece_x2_plain<false>(v, 1.f, reinterpret_cast<uint4*>(im + loff));
+            }
+        }
+    };
+    auto fragB = [&](const uint16_t* im, int tile, bf16x8 (&f)[3]) {
+        const bf16x8* p = reinterpret_cast<const bf16x8*>(im + tile * kB) + lane;
+#pragma unroll
+        for (int q = 0; q < 2; q++) f[q] = p[64 * q];
+    };
+    // dY's transposed read (k_wgrad_tr's): lane 4 q + p of row group c supplies row 8 c + q, piece p of the tile
+    const int tc = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+    const uint32_t laneA = (uint32_t)(16 * ((8 * tc + tq) * wpA + tp));  // bytes
+    typedef short s4v __attribute__((ext_vector_type(4)));
+    auto tr = [&](const char* p) {
+        return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(p));
+    };
+    auto fragA = [&](const char* stage, int tile, bf16x8 (&f)[3]) {
+        const char* p = stage + laneA + 64 * tile;
+        constexpr int r4 = 16 * 4 * wpA;  // four rows on, bytes
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const s4v u = tr(p + 8 * q), v = tr(p + 8 * q + r4);
+            f[q] = bf16x8{u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+        }
+    };
+
+    f32x4 acc[RN * NTK + EX], accx[RN * NTK + EX];
+#pragma unroll
+    for (int u = 0; u < RN * NTK + EX; u++) acc[u] = accx[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nsteps = (nrows + 31) / 32;
+    constexpr std::integral_constant<int, 0> c0{};
+    constexpr std::integral_constant<int, 1> c1{};
+    // the step's MFMAs: A fragments a / ax held, B from image im; `mid` runs after the first k-tile's MFMAs
+    auto mfmas = [&](const uint16_t* im, const bf16x8 (&a)[RN][3], const bf16x8 (&ax)[3], bf16x8 (&b)[2][3],
+                     auto&& mid) {
+#pragma unroll
+        for (int tk = 0; tk < NTK; tk++) {
+            if (tk + 1 < NTK) fragB(im, tk + 1, b[(tk + 1) & 1]);
+            if (tk < live) {  // workgroup-uniform
+#pragma unroll
+                for (int r = 0; r < RN; r++)
+                    acc[r * NTK + tk] = mma<P>(a[r], b[tk & 1], acc[r * NTK + tk], accx[r * NTK + tk]);
+            }
+            if (tk == 0) mid();
+        }
+#pragma unroll
+        for (int e = 0; e < EX; e++) {
+            int j = wave + kWgWaves * e;  // leftover tile j (clamped: a duplicate, not stored)
+            j = j < kRem ? j : kRem - 1;
+            if (j % NTK < live) {  // wave-uniform
+                bf16x8 b1[3];
+                fragB(im, j % NTK, b1);
+                acc[RN * NTK + e] = mma<P>(ax, b1, acc[RN * NTK + e], accx[RN * NTK + e]);
+            }
+        }
+    };
+    if constexpr (!kOverlap) {
+        issueA(c0, 0);
+        issueB(c0, 0);
+        if (nsteps > 1) {
+            issueA(c1, 1);
+            issueB(c1, 1);
+        }
+        wait_stage(nsteps > 1);
+        barrier();
+        convB(reinterpret_cast<const float*>(rawB), img);
+        barrier();
+        auto step = [&](auto tcur, int st) {  // step st in stage T = st & 1; stage 1 - T holds step st + 1
+            constexpr int T = decltype(tcur)::value;
+            const char* stage = reinterpret_cast<const char*>(rawA + T * kSecA);
+            bf16x8 a[RN][3], ax[3], b[2][3];
+#pragma unroll
+            for (int r = 0; r < RN; r++) fragA(stage, RN * wave + r, a[r]);
+            if constexpr (EX > 0) fragA(stage, kWgWaves * RN, ax);  // the leftover tiles' n-tile
+            fragB(img, 0, b[0]);
+            barrier();  // every wave holds its A fragments: stage T is free
+            if (st + 2 < nsteps) {
+                issueA(tcur, st + 2);
+                issueB(tcur, st + 2);
+            }
+            mfmas(img, a, ax, b, [] {});
+            if (st + 1 < nsteps) {
+                wait_stage(st + 2 < nsteps);  // step st + 1's DMAs (this wave) landed
+                barrier();  // the MFMAs' reads of the image are done; step st + 1's stage is visible
+                convB(reinterpret_cast<const float*>(rawB + (1 - T) * kSecB), img);
+                barrier();  // the image holds step st + 1's X
+            }
+        };
+        for (int st = 0; st < nsteps; st += 2) {
+            step(c0, st);
+            if (st + 1 < nsteps) step(c1, st + 1);
+        }
+    } else {
+        // WG_MIX_OVERLAP: X one step further ahead than dY, and two images -- step st + 1's X is converted into
+        // the other image after the first k-tile's MFMAs of step st.  ONE barrier per step: before it the wave
+        // waited for all its DMAs (vmcnt(0)), so after it dY of step st, the raw X of step st + 1 and the image
+        // of step st are visible, and every wave is past step st - 1 (its A fragments read, its image read, its
+        // conversion's raw X read) -- free for dY of step st + 1, the raw X of step st + 2 and the conversion
+        // of step st + 1
+        issueA(c0, 0);
+        issueB(c0, 0);
+        if (nsteps > 1) issueB(c1, 1);
+        wait_stage(false);
+        barrier();
+        convB(reinterpret_cast<const float*>(rawB), img);
+        auto step = [&](auto tcur, int st) {
+            constexpr int T = decltype(tcur)::value;
+            constexpr std::integral_constant<int, 1 - T> cn{};
+            barrier();
+            if (st + 1 < nsteps) issueA(cn, st + 1);
+            if (st + 2 < nsteps) issueB(tcur, st + 2);
+            const char* stage = reinterpret_cast<const char*>(rawA + T * kSecA);
+            const uint16_t* im = img + T * kImg;
+            bf16x8 a[RN][3], ax[3], b[2][3];
+#pragma unroll
+            for (int r = 0; r < RN; r++) fragA(stage, RN * wave + r, a[r]);
+            if constexpr (EX > 0) fragA(stage, kWgWaves * RN, ax);
+            fragB(im, 0, b[0]);
+            mfmas(im, a, ax, b, [&] {
+                if (st + 1 < nsteps)
+                    convB(reinterpret_cast<const float*>(rawB + (1 - T) * kSecB), img + (1 - T) * kImg);
+            });
+            wait_stage(false);  // this wave's DMAs of dY (step st + 1) and X (step st + 2) landed
+        };
+        for (int st = 0; st < nsteps; st += 2) {
+            step(c0, st);
+            if (st + 1 < nsteps) step(c1, st + 1);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (every issued DMA was waited for before its step)
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+#pragma unroll
+        for (int k = 0; k < kSlotA; k++) asm volatile("" ::"v"(obA[t][k]));
+#pragma unroll
+        for (int k = 0; k < kSlotB; k++) asm volatile("" ::"v"(obB[t][k]));
+    }
+    asm volatile("" ::"s"(rsA), "s"(rsB), "s"(stepA), "s"(stepB));
+    uint32_t rm = 0;  // the range guard, over the stored accumulators only (the others may hold anything)
+    float* out = ws + (size_t)s * N * K;
+    auto put = [&](f32x4 v, f32x4 vx, int tn, int tk) {
+        v = x2_combine<P>(v, vx);
+        const int col = col0 + 16 * tk + (lane & 15);
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int row = 16 * tn + 4 * (lane >> 4) + g;
+            if (row < N && col < K) {
+                rm = max(rm, __float_as_uint(v[g]) & 0x7FFFFFFFu);
+                out[(size_t)row * K + col] = v[g] * cscale;
+            }
+        }
+    };
+#pragma unroll
+    for (int r = 0; r < RN; r++)
+#pragma unroll
+        for (int tk = 0; tk < NTK; tk++) put(acc[r * NTK + tk], accx[r * NTK + tk], RN * wave + r, tk);
+#pragma unroll
+    for (int e = 0; e < EX; e++) {
+        const int j = wave + kWgWaves * e;
+        if (j < kRem) put(acc[RN * NTK + e], accx[RN * NTK + e], kWgWaves * RN + j / NTK, j % NTK);
+    }
+    range_note<P>(rm);
+}
+
 // out[e] = sum over the row slices s of ws[s][e]: 16 groups of consecutive slices per element, each group's
 // loads all in flight (the plain per-element loop over S = 256 slices was latency-bound: ~90 us), the
 // groups then summed in order -- a fixed order, so the result is deterministic
@@ -3465,10 +3790,8 @@ static int dispatch_bres_c(const float* a, int lda, float ascale, const uint16_t
     }
     if (ep.mbits_out) return launch_bres<P, C, EM_FWD, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
     if (ep.mbits_in) return launch_bres<P, C, EM_BWD, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
-    if constexpr (VW == 32)
-        return MM_E_ARG;  // x2 planes A: the hidden layers' forms only (with bits)
-    else
-        return launch_bres<P, C, EM_F32, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
+    // (x2 planes A without bits: the input gradient into the fp32-stored h0, dY1 W1)
+    return launch_bres<P, C, EM_F32, VW>(a, lda, ascale, b, M, N, K, pl, ep, s);
 }
 
 template <int P, int VW>
@@ -3520,16 +3843,19 @@ static int gemm_nt_f32a(int prec, const float* a, int lda, float ascale, const u
     if (ap || cp) {
         if (prec != MM_PREC_X2 || mask || c_tp || a16 || c16) return MM_E_ARG;
         if (!a || (K & 3) || (lda & 3) || lda < K || ((uintptr_t)a & 15)) return MM_E_ARG;  // 16-byte rows
-        if (ap && (ascale != 1.f || (!mbits_in && !mbits_out))) return MM_E_ARG;  // (plane A: through ReLU bits)
+        // plane A: at scale 1; without ReLU bits (the input gradient into an fp32-stored layer input) on the
+        // B-resident kernel only, in one row chunk (see below)
+        const bool plain_a = ap && !mbits_in && !mbits_out;
+        if (ap && ascale != 1.f) return MM_E_ARG;
         if (cp && ((!mbits_out && !mbits_in) || (N & 3) || (ldc & 3) || ((uintptr_t)c & 15))) return MM_E_ARG;
         if ((mbits_in || mbits_out) && (N > 16 * 17 || (mbits_in && mbits_out))) return MM_E_ARG;
         if (mbits_in && (bias || relu)) return MM_E_ARG;
         if (colsum && (!mbits_in || !c)) return MM_E_ARG;
-        if (M == 0) return 0;
+        if (M == 0) return plain_a ? MM_E_ARG : 0;
         const size_t wmaxp = std::max(std::max((size_t)lda, (size_t)ldc), (size_t)N);
         const size_t capp = ((((size_t)1 << 31) - 1) / (4 * wmaxp) - 32) / kRowPad * kRowPad;
         if ((size_t)M > capp) {  // row chunks, as below
-            if (capp < (size_t)kRowPad) return MM_E_ARG;
+            if (capp < (size_t)kRowPad || plain_a) return MM_E_ARG;
             for (size_t m0 = 0; m0 < (size_t)M; m0 += capp) {
                 const int mr = (int)std::min(capp, (size_t)M - m0);
                 const size_t rt0 = m0 / 16;
@@ -3549,6 +3875,7 @@ static int gemm_nt_f32a(int prec, const float* a, int lda, float ascale, const u
         int cfgp = C_PAIR;
         // the kernel choice of the fp32-storage call below (same plan, same row chunks)
         const bool bres = bres_enabled() && bres_plan(prec, M, N, K, lda, ldc, mbits_in || mbits_out, plp, cfgp);
+        if (plain_a && !bres) return MM_E_ARG;  // (the streaming kernel takes a plane A through ReLU bits only)
         if (ap)
             return bres ? dispatch_bres<P_X2, 32>(a, lda, 1.f, b_tp, M, N, K, plp, cfgp, epp, sp)
                         : dispatch_nt<P_X2, ASrcX2PV>(a, lda, 1.f, b_tp, M, N, K, epp, sp);
@@ -3952,6 +4279,17 @@ static int launch_tr_t(const WgPlan& p, const uint32_t* dy, int lddy, const uint
 
 static bool wg_x2p_shape(const WgPlan& p) { return p.TN == 17 && p.NTK == 9; }  // the 264 x 264 layers' blocks
 
+// the mixed kernel (k_wgrad_mix): dY as x2 planes (lddy its row pitch in 4-byte units), X fp32
+template <int TN, int NTK>
+static int launch_mix_t(const WgPlan& p, const uint32_t* dy, int lddy, const float* x, int ldx, int M, int N, int K,
+                        float cscale, float* ws, hipStream_t s) {
+    hipLaunchKernelGGL((k_wgrad_mix<TN, NTK>), dim3(rup(p.nslices, 8) * p.ncb), dim3(kWgThreads), 0, s, dy, lddy, x,
+                       ldx, M, N, K, p.rows, p.nslices, p.ncb, cscale, ws);
+    return (int)hipGetLastError();
+}
+
+static bool wg_mix_shape(const WgPlan& p) { return p.TN == 17 && p.NTK == 8; }  // the 264 x 460 layer's blocks
+
 template <int P, int XB = 4, int AB = 4>
 static int launch_rect_p(const WgPlan& p, const float* dy, int lddy, float dscale, const float* x, int ldx, int M,
                          int N, int K, float cscale, float* ws, hipStream_t s) {
@@ -4003,19 +4341,23 @@ static int gemm_wgrad(int prec, const float* dy, int lddy, float dscale, const f
     if (M < 0 || N <= 0 || K <= 0 || N > 16 * kWgMaxT || lddy < N || ldx < K) return MM_E_ARG;
     if (flags & ~(MM_GEMM_B_F16 | MM_GEMM_A_F16 | MM_GEMM_A_X2P | MM_GEMM_B_X2P)) return MM_E_ARG;
     const bool x16 = flags & MM_GEMM_B_F16, a16 = flags & MM_GEMM_A_F16;  // a16: dY fp16 (pre-scaled)
-    if (flags & (MM_GEMM_A_X2P | MM_GEMM_B_X2P)) {  // both operands as x2 planes (dY pre-scaled: dscale 1): k_wgrad_tr
-        if (flags != (MM_GEMM_A_X2P | MM_GEMM_B_X2P) || prec != MM_PREC_X2 || dscale != 1.f) return MM_E_ARG;
+    // dY as x2 planes (pre-scaled: dscale 1) with X as planes too (k_wgrad_tr) or fp32 (A_X2P alone: k_wgrad_mix)
+    if (flags & (MM_GEMM_A_X2P | MM_GEMM_B_X2P)) {
+        const bool mix = flags == MM_GEMM_A_X2P;
+        if ((!mix && flags != (MM_GEMM_A_X2P | MM_GEMM_B_X2P)) || prec != MM_PREC_X2 || dscale != 1.f)
+            return MM_E_ARG;
         hipStream_t sp = (hipStream_t)stream;
         if (M == 0) return dw ? (int)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, sp) : MM_E_ARG;
-        if (!dy || !x || !ws || (N & 3) || (K & 3) || (lddy & 3) || (ldx & 3) ||
+        if (!dy || !x || !ws || (N & 3) || (!mix && (K & 3)) || (lddy & 3) || (ldx & 3) ||
             (((uintptr_t)dy | (uintptr_t)x) & 15) || (size_t)M * lddy * 4 >= ((size_t)1 << 31) ||
             (size_t)M * ldx * 4 >= ((size_t)1 << 31))
             return MM_E_ARG;
         const WgPlan pp = wg_plan(prec, M, N, K);
-        if (!wg_x2p_shape(pp)) return MM_E_ARG;
+        if (!(mix ? wg_mix_shape(pp) : wg_x2p_shape(pp))) return MM_E_ARG;
         const uint32_t* dyp = reinterpret_cast<const uint32_t*>(dy);
         const uint32_t* xp = reinterpret_cast<const uint32_t*>(x);
-        const int ep = launch_tr_t<17, 9>(pp, dyp, lddy, xp, ldx, M, N, K, cscale, ws, sp);
+        const int ep = mix ? launch_mix_t<17, 8>(pp, dyp, lddy, x, ldx, M, N, K, cscale, ws, sp)
+                           : launch_tr_t<17, 9>(pp, dyp, lddy, xp, ldx, M, N, K, cscale, ws, sp);
         if (ep || !dw) return ep;
         const long np = (long)N * K;
         hipLaunchKernelGGL(k_wg_reduce, dim3((unsigned)((np + 15) / 16)), dim3(256), 0, sp, ws, pp.nslices, np, dw);
@@ -4073,6 +4415,26 @@ extern "C" int mm_gemm_x2p_ok(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0 || N > 16 * kWgMaxT || (N & 3) || (K & 3)) return 0;
     if ((size_t)(M + 16) * std::max(N, K) * 4 >= ((size_t)1 << 31)) return 0;
     return wg_x2p_shape(wg_plan(MM_PREC_X2, M, N, K)) ? 1 : 0;
+}
+
+// the x2 plane-A input gradient without ReLU bits ([M, N] planes -> fp32 [M, K]: the layer below stores its
+// input fp32) runs on the B-resident kernel only, in one row chunk
+static bool x2p_plain_a_ok(int M, int N, int K, int lda, int ldc) {
+    if (M <= 0 || N <= 0 || K <= 0 || (N & 3) || (lda & 3) || lda < N || ldc < K) return false;
+    const size_t wmax = std::max(std::max((size_t)lda, (size_t)ldc), (size_t)K);
+    if ((size_t)M > ((((size_t)1 << 31) - 1) / (4 * wmax) - 32) / kRowPad * kRowPad) return false;
+    BresPlan pl;
+    int cfg = C_PAIR;
+    return bres_enabled() && bres_plan(MM_PREC_X2, M, K, N, lda, ldc, false, pl, cfg);
+}
+
+// whether the input gradient dY [M, N] of the x2 layer [M, K] -> [M, N] can be stored as (pre-scaled) planes
+// beside an fp32 layer input X [M, K]: the weight gradient dW [N, K] has k_wgrad_mix's blocks, and the plain
+// plane-A input gradient dY W runs at M rows under the current GEMM algorithm
+extern "C" int mm_gemm_x2p_dy_ok(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0 || N > 16 * kWgMaxT || (N & 3) || (K & 3)) return 0;
+    if ((size_t)(M + 16) * std::max(N, K) * 4 >= ((size_t)1 << 31)) return 0;
+    return wg_mix_shape(wg_plan(MM_PREC_X2, M, N, K)) && x2p_plain_a_ok(M, N, K, N, K) ? 1 : 0;
 }
 
 extern "C" int mm_gemm_wgrad_slices(int prec, int M, int N, int K) {

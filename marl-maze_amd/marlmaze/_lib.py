@@ -70,7 +70,7 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_actor_front_fwd_h16_ex", "mm_head_act", "mm_act", "mm_eval_init", "mm_eval_accum",
            "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum",
            "mm_elog_state_words", "mm_elog_init", "mm_elog_start", "mm_elog_step",
-           "mm_gemm_x2p_ok", "mm_x3_heads_bwd_x2p",
+           "mm_gemm_x2p_ok", "mm_gemm_x2p_dy_ok", "mm_x3_heads_bwd_x2p",
            "mm_critic_update_ok", "mm_critic_update")
 VERSION = 308  # mm_version() this binding is written for
 
@@ -286,6 +286,7 @@ def lib():
                            ("mm_actor_front_fwd_h16", [P, P, i32, i32, i32, P, P]),
                            ("mm_actor_front_fwd_h16_ex", [P, P, i32, i32, i32, P, i32, P]),
                            ("mm_gemm_x2p_ok", [i32, i32, i32]),
+                           ("mm_gemm_x2p_dy_ok", [i32, i32, i32]),
                            ("mm_x3_heads_bwd_x2p", [P, i32, P, P, i32, i32, P, P, f32, P]),
                            ("mm_critic_update_ok", [i32, i32, i32]),
                            ("mm_critic_update", [P, i32, i32, i32] + [P] * 18),

@@ -217,7 +217,7 @@ def _grad_scale(M, prec):
 
 def _wgrad(dy, x, prec, out=None, nk=None):
     """dW = dY^T X (mm_gemm_wgrad).  An fp16 dY is the f16 networks' pre-scaled input gradient; dY and X as
-    x2 planes (X2_PLANES; dY pre-scaled): nk = (N, K)."""
+    x2 planes (X2_PLANES; dY pre-scaled), or a plane dY with the fp32 h0 (X2_DY1): nk = (N, K)."""
     from . import x3
 
     s = _grad_scale(dy.shape[0], prec)
@@ -243,6 +243,11 @@ F16_H0 = os.environ.get("MARLMAZE_F16_H0", "1") != "0"
 # kernel with nothing to convert).  The input gradients are stored pre-scaled by _grad_scale, as the f16 networks' are.  Results
 # are bit-identical to fp32 storage.  MARLMAZE_X2_PLANES=0 keeps fp32 storage (A/B runs).
 X2_PLANES = os.environ.get("MARLMAZE_X2_PLANES", "1") != "0"
+# ... and dY1, the gradient into the first trunk layer (whose input h0 stays fp32), with them from the B-resident
+# GEMM's row threshold up: the 264 x 460 weight gradient reads the plane dY beside the fp32 h0 (k_wgrad_mix: no
+# dY conversion, which its four column blocks each repeated), the 460-wide input gradient a plane A without ReLU
+# bits.  Bit-identical again.  MARLMAZE_X2_DY1=0 keeps dY1 fp32 (A/B runs).
+X2_DY1 = os.environ.get("MARLMAZE_X2_DY1", "1") != "0"
 
 # x2 critic: the update's three forward GEMMs, dV, the head's backward and the input-gradient GEMM as one launch
 # (mm_critic_update, Critic.train_update_fused) from the B-resident GEMM's row threshold upwards; every value
@@ -348,8 +353,9 @@ def _mlp_bwd(ctx_bits, hs, ws, dy, cs, prec, need_dx, outs=None):
     outs: destinations [dW0, db0, dW1, db1, ...] (or None: allocated).
     An fp16 dY is the f16 networks' pre-scaled input gradient (fp16(dY s), see
     _g16): the layers' input gradients then stay fp16 pre-scaled too.  A dY as
-    x2 planes (pre-scaled, X2_PLANES) goes with hs[l] as planes; the gradient
-    into a layer whose input is stored fp32 (h0) is fp32 again.
+    x2 planes (pre-scaled, X2_PLANES) goes with hs[l] as planes, or with the
+    fp32 h0 at the first layer (X2_DY1, where x3.x2p_dy_ok); elsewhere the
+    gradient into a layer whose input is stored fp32 is fp32 again.
     Returns (dx or None, [dW0, db0, dW1, db1, ...])."""
     from . import x3
 
@@ -370,8 +376,12 @@ def _mlp_bwd(ctx_bits, hs, ws, dy, cs, prec, need_dx, outs=None):
         if l > 0:  # dY of layer l-1 = (dY W) * (h_l > 0): the ReLU bits of layer l-1's forward
             cs = x3.colsum_buf(M, ws[l].shape[1], dy.device)
             out = torch.empty((M, ws[l].shape[1]), dtype=torch.float16, device=dy.device) if g16 else None
-            if x3.is_planes(dy):  # planes again where the layer below stores its input as planes
-                out = x3.planes(M, ws[l].shape[1], dy.device) if x3.is_planes(hs[l - 1]) else None
+            if x3.is_planes(dy):
+                # planes again where the layer below stores its input as planes -- or, into the first layer
+                # (X2_DY1: h0 is fp32), where its weight gradient and input gradient take a plane dY beside it
+                below = x3.is_planes(hs[l - 1]) or (l == 1 and X2_PLANES and X2_DY1 and hs[0].dtype == torch.float32
+                                                    and x3.x2p_dy_ok(M, *ws[0].shape))
+                out = x3.planes(M, ws[l].shape[1], dy.device) if below else None
             dy = x3.gemm(dy, wt, mbits_in=ctx_bits[l - 1], colsum=cs, ascale=ascale, cscale=cscale, out=out,
                          oscale=s)
         elif need_dx:

@@ -332,6 +332,13 @@ def x2p_ok(M, N, K):
     return bool(_lib.lib().mm_gemm_x2p_ok(int(M), int(N), int(K)))
 
 
+def x2p_dy_ok(M, N, K):
+    """Whether the input gradient dY [M, N] of the x2 layer [M, K] -> [M, N] can be stored as planes beside an
+    fp32 layer input (mm_gemm_x2p_dy_ok: the mixed weight gradient [N, K] and the plain plane-A input gradient
+    of width K both run at M rows under the current set_algo setting)."""
+    return bool(_lib.lib().mm_gemm_x2p_dy_ok(int(M), int(N), int(K)))
+
+
 def a16_ok(M, N, K):
     """Whether an f16 GEMM of that shape takes fp16 A (mm_gemm_a16_ok: the B-resident kernel's shapes)."""
     return bool(_lib.lib().mm_gemm_a16_ok(int(M), int(N), int(K), int(K), int(N)))
@@ -372,14 +379,19 @@ def wgrad(dy, x, prec="x3", dscale=1.0, out=None, checked=False, cscale=None, nk
     Inside a ``deferred()`` scope with ``out`` given, the row-slice partials'
     sum runs when the scope ends.  checked (x2 / f16): as gemm()'s -- redone at
     x3 when an operand left the fp16 range.  dY and X both as x2 planes (planes(); prec x2, dscale 1, cscale the
-    inverse of dY's scale): nk = (N, K), the logical widths."""
+    inverse of dY's scale): nk = (N, K), the logical widths.  A plane dY with an fp32 X (the first trunk layer,
+    whose input h0 is stored fp32) takes the mixed form, same arguments."""
     if is_planes(dy) or is_planes(x):
-        assert is_planes(dy) and is_planes(x) and prec == "x2" and not checked and float(dscale) == 1.0
+        assert is_planes(dy) and prec == "x2" and not checked and float(dscale) == 1.0
         N, K = nk
         M = dy.shape[0]
-        assert x.shape[0] == M and _plane_rows(dy) and _plane_rows(x)
-        assert dy.shape[1] == N // 4 and x.shape[1] == K // 4, (dy.shape, x.shape, nk)
-        flags = _lib.GEMM_A_X2P | _lib.GEMM_B_X2P
+        assert x.shape[0] == M and _plane_rows(dy) and dy.shape[1] == N // 4, (dy.shape, x.shape, nk)
+        if is_planes(x):
+            assert _plane_rows(x) and x.shape[1] == K // 4, (x.shape, nk)
+            flags = _lib.GEMM_A_X2P | _lib.GEMM_B_X2P
+        else:  # the mixed form (k_wgrad_mix)
+            assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == K, (x.shape, nk)
+            flags = _lib.GEMM_A_X2P
     elif checked and prec != "x3":
         if dy.dtype == torch.float16 or x.dtype == torch.float16 or cscale is not None:
             # the x3 redo reads fp32 operands and has no output scale: a pre-scaled fp16 dY would come back

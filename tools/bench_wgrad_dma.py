@@ -1,10 +1,14 @@
 """x2 trunk weight gradients: k_wgrad_tr (operands stored as x2 planes, three raw stages, no conversion)
 against k_wgrad_dma (fp32 operands, LDS-DMA staging, two raw stages in flight) and k_wgrad_rect (register
 staging), alternating in one process, HIP events, median and min .. max of ROUNDS x 10 launches; algorithmic
-bytes 4 M (N + K) per launch.  Then the 264 x 264 forward and input-gradient GEMMs (k_bres) from plane A /
+bytes 4 M (N + K) per launch.  At 264 x 460 k_wgrad_mix (dY as planes beside the fp32 X) joins them.  Then the 264 x 264 forward and input-gradient GEMMs (k_bres) from plane A /
 into planes against fp32 storage, the same way.  One JSON line per shape.
 
   python tools/bench_wgrad_dma.py [M]
+
+MIX_LIBS=name:path[,name:path...] adds k_wgrad_mix of other builds of the library (tools/ab_build.py: e.g. the
+form with -DWG_MIX_OVERLAP=1, or "base" for the parent commit's k_wgrad_dma) to the 264 x 460 alternation as
+mix_NAME (dma_NAME for a build without the mixed kernel).
 """
 import json
 import os
@@ -14,7 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "marl-maze_amd"))
-from marlmaze import x3  # noqa: E402
+from marlmaze import _lib, x3  # noqa: E402
 
 ROUNDS = 7
 
@@ -38,6 +42,27 @@ def to_planes(x, s=1.0):
     return p
 
 
+def other_libs():
+    """MIX_LIBS -> {name: loaded library}; the default library stays the one in use."""
+    out, main = {}, _lib.lib()
+    for item in filter(None, os.environ.get("MIX_LIBS", "").split(",")):
+        name, path = item.split(":", 1)
+        _lib.LIB_PATH, _lib._LIB = os.path.abspath(path), None
+        out[name] = _lib.lib()
+    _lib._LIB = main
+    return out, main
+
+
+def with_lib(L, main, f):
+    def run():
+        _lib._LIB = L
+        try:
+            f()
+        finally:
+            _lib._LIB = main
+    return run
+
+
 def alternate(forms):
     """forms: name -> callable; the median and the spread of each, alternating."""
     res = {k: [] for k in forms}
@@ -56,7 +81,9 @@ for N, K in ((264, 264), (264, 460)):
     dy = torch.randn(M, N, device="cuda", generator=g) / M
     x = torch.randn(M, K, device="cuda", generator=g)
     planes = x3.x2p_ok(M, N, K)  # (k_wgrad_tr has the 264 x 264 layers' blocks only)
-    dyp, xp = (to_planes(dy, s), to_planes(x)) if planes else (None, None)
+    mixed = x3.x2p_dy_ok(M, N, K)  # (k_wgrad_mix has the 264 x 460 layer's blocks only)
+    dyp = to_planes(dy, s) if planes or mixed else None
+    xp = to_planes(x) if planes else None
     out = torch.empty(N, K, device="cuda")
 
     def algo(name):
@@ -68,6 +95,17 @@ for N, K in ((264, 264), (264, 460)):
     forms = {"dma": algo("dma"), "reg": algo("reg")}
     if planes:
         forms["tr"] = lambda: x3.wgrad(dyp, xp, prec="x2", dscale=1.0, cscale=1.0 / s, out=out, nk=(N, K))
+    if mixed:
+        def mix():
+            x3.wgrad(dyp, x, prec="x2", dscale=1.0, cscale=1.0 / s, out=out, nk=(N, K))
+
+        forms["mix"] = mix
+        libs, main = other_libs()
+        for name, L in libs.items():
+            if hasattr(L, "mm_gemm_x2p_dy_ok"):
+                forms["mix_" + name] = with_lib(L, main, mix)
+            else:
+                forms["dma_" + name] = with_lib(L, main, algo("dma"))
     r = alternate(forms)
     x3.set_wgrad_algo("dma")
     byt = 4.0 * M * (N + K)
@@ -79,6 +117,8 @@ for N, K in ((264, 264), (264, 460)):
     line["speedup"] = round(line["reg_us"] / line["dma_us"], 3)
     if planes:
         line["tr_speedup"] = round(line["dma_us"] / line["tr_us"], 3)
+    if mixed:
+        line["mix_speedup"] = round(line["dma_us"] / line["mix_us"], 3)
     print(json.dumps(line), flush=True)
     del dy, x, dyp, xp
 
