@@ -6,8 +6,8 @@ into planes against fp32 storage, the same way.  One JSON line per shape.
 
   python tools/bench_wgrad_dma.py [M]
 
-MIX_LIBS=name:path[,name:path...] adds k_wgrad_mix of other builds of the library (tools/ab_build.py: e.g. the
-form with -DWG_MIX_OVERLAP=1, or "base" for the parent commit's k_wgrad_dma) to the 264 x 460 alternation as
+MIX_LIBS=name:path[,name:path...] adds k_wgrad_mix of other builds of the library (tools/ab_build.py: e.g. a
+diagnostic build with -DWG_NO_MFMA, or "base" for the parent commit's kernel) to the 264 x 460 alternation as
 mix_NAME (dma_NAME for a build without the mixed kernel).
 """
 import json
