@@ -3,13 +3,18 @@ builds, median of REPS rounds of 10 launches each (HIP events):
 
   LIBS=tools/_var/base.so,marl-maze_amd/libmarlmaze.so CASES=... python tools/ab_libs.py
 
+SWAP=1 reverses the builds' order every other round (the place in the alternation alone moves a kernel by 20-30
+us: DESIGN.md section 4); JSONL=path appends one JSON line per case with the medians and each build's min-max.
+
 CASES (comma-separated; M = rows, default 419,430):
   gemm:PREC:FORM:NxK[:ALGO]   FORM fwd (bias+ReLU+bits), bwd (through bits + column sums), plain; ALGO auto
                        (default) or stream (x3.set_algo)
   wgrad:PREC:NxK       dW = dY^T X
   front:fwd / front:bwd  the fused actor front-end (M samples)
+  critic:update        the x2 critic's fused update (mm_critic_update, its weight gradients and sums)
 """
 import ctypes
+import json
 import os
 import sys
 
@@ -61,6 +66,18 @@ def make(c, M, g):
         xx = torch.randn(M, K, device="cuda", generator=g)
         out = torch.empty(N, K, device="cuda")
         return lambda: x3.wgrad(dy, xx, prec=prec, out=out)
+    if parts[0] == "critic":  # critic:update -- the fused per-row critic update (mm_critic_update) and its launches
+        from marlmaze.networks import Critic
+
+        torch.manual_seed(0)
+        critic = Critic(2, hidden_sizes=[64, 64], gemm_prec="x2").cuda()
+        xc = torch.randn(M, 130, device="cuda", generator=g)
+        rtg = torch.randn(M, device="cuda", generator=g)
+
+        def run():
+            with x3.cached_packs():
+                critic.train_update_fused(xc, rtg)
+        return run
     if parts[0] == "front":
         from marlmaze.networks import Actor, _front_bwd_to, _front_fwd, front_params
 
@@ -92,6 +109,7 @@ def main():
     Ls = [load(os.path.join(REPO, p) if not os.path.isabs(p) else p) for p in libs]
     M = int(os.environ.get("M", 419430))
     reps = int(os.environ.get("REPS", 5))
+    swap = os.environ.get("SWAP", "0") == "1"
     g = torch.Generator(device="cuda").manual_seed(0)
     for c in os.environ.get("CASES", DEFAULT).split(","):
         fns = []
@@ -101,13 +119,19 @@ def main():
             fns[-1]()
         torch.cuda.synchronize()
         t = [[] for _ in Ls]
-        for _ in range(reps):
-            for k, L in enumerate(Ls):
-                _lib._LIB = L
+        for r in range(reps):
+            order = range(len(Ls)) if not (swap and r % 2) else reversed(range(len(Ls)))
+            for k in order:  # SWAP=1: the builds' order reversed every other round
+                _lib._LIB = Ls[k]
                 t[k].append(timed(fns[k]))
         med = [sorted(v)[len(v) // 2] for v in t]
         print(f"{c:24s} M={M}: " + "  ".join(f"{os.path.basename(p)} {m:8.1f} us" for p, m in zip(libs, med)) +
               f"  ratio {med[-1] / med[0]:.3f}", flush=True)
+        if os.environ.get("JSONL"):  # one line per case: medians and each build's min-max over the rounds
+            with open(os.environ["JSONL"], "a") as f:
+                f.write(json.dumps(dict(case=c, M=M, rounds=reps, swap=swap, libs=[os.path.basename(p) for p in libs],
+                                        median_us=[round(m, 1) for m in med], min_us=[round(min(v), 1) for v in t],
+                                        max_us=[round(max(v), 1) for v in t])) + "\n")
         del fns
         torch.cuda.empty_cache()
 

@@ -1,13 +1,15 @@
 """Compare what two builds emit for the same kernels: two assembly listings of one source (hipcc ... -S), kernel by
 kernel.
 
-  python tools/kernel_isa_diff.py A.s B.s [name-regex] [--full] [--classes v_mfma,ds_read,...]
+  python tools/kernel_isa_diff.py A.s B.s [name-regex] [--full] [--classes v_mfma,ds_read,...] [--window loop|all]
 
 For every kernel symbol (mangled or demangled name) matching the regex and present in both listings it prints,
 for each side, the opcode histogram (only the rows that differ unless --full), the opcode sequence of the
 chosen classes inside the loop window -- from the first staging or LDS-DMA load (the first buffer_load* /
 global_load* outside the ;;wg-partial markers) to the kernel's last s_barrier, the window
 tools/check_wgrad_operands.py delimits -- run-length encoded, and the "; Kernel info:" figures.
+--window all takes the whole kernel body as the window: for kernels whose last barrier precedes their main
+loops (k_bres, k_critic_update, k_trunk3), which the loop window would cut off before them.
 
 Opcodes are classified by prefix only (v_mfma, buffer_load, global_load, ds_read, ds_write, s_barrier,
 s_waitcnt).  Exit status 1 when, for some kernel, B differs from A in
@@ -61,7 +63,9 @@ def cls(op, classes):
     return next((c for c in classes if op.startswith(c)), None)
 
 
-def window(ops, classes):
+def window(ops, classes, whole=False):
+    if whole:
+        return [o for o, _ in ops if cls(o, classes)]
     first = next((i for i, (o, part) in enumerate(ops) if o.startswith(("buffer_load", "global_load")) and not part), None)
     last = max((i for i, (o, _) in enumerate(ops) if o.startswith("s_barrier")), default=None)
     if first is None or last is None or last < first:
@@ -88,6 +92,13 @@ def main():
         if i + 1 >= len(argv):
             sys.exit("--classes takes a comma-separated list of opcode prefixes")
         classes = tuple(argv[i + 1].split(","))
+        del argv[i:i + 2]
+    whole = False
+    if "--window" in argv:
+        i = argv.index("--window")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("loop", "all"):
+            sys.exit("--window takes loop or all")
+        whole = argv[i + 1] == "all"
         del argv[i:i + 2]
     args = [a for a in argv if not a.startswith("--")]
     if len(args) < 2:
@@ -118,7 +129,7 @@ def main():
         print("   classes: " + ", ".join(
             f"{c} {sum(n for o, n in ha.items() if cls(o, classes) == c)}/{sum(n for o, n in hb.items() if cls(o, classes) == c)}"
             for c in classes))
-        wa, wb = window(oa, classes), window(ob, classes)
+        wa, wb = window(oa, classes, whole), window(ob, classes, whole)
         if wa == wb:
             print(f"   window: equal ({len(wa)} instructions of the chosen classes)")
             if full:
