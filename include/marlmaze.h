@@ -447,6 +447,42 @@ int mm_ppo_loss(const float* heads, const uint8_t* masks, const int8_t* actions,
 int mm_ppo_loss_bwd(const float* heads, const uint8_t* masks, const int8_t* actions, const float* coef,
                     const float* dloss, int M, float* dheads, void* stream);
 
+/* The same policy loss with an entropy bonus and the update's diagnostics (no
+ * reference counterpart: PPO.py:62-79 minimises the clipped surrogate alone and
+ * reports two losses).  Operands as mm_ppo_loss.  Per sample, H_i = the sum
+ * over its two agent rows of H_move + H_mark: H_move = -sum over legal j of
+ * p_j log p_j for the masked softmax p (a p_j that underflowed to 0
+ * contributes 0; a row with no legal move has H_move = 0), H_mark = the
+ * Bernoulli entropy log1p(t) + a t / (1 + t), a = |z_5|, t = exp(-a), where the
+ * mark is allowed, else 0.  The loss is surrogate - ent_coef * mean_i H_i.
+ * mm_ppo_loss_ent: coef and partial as mm_ppo_loss (equal values: partial is
+ * the surrogate alone, whatever ent_coef), and stat_partial
+ * [mm_ppo_loss_partials(M), MM_PPO_STAT_WORDS] per-workgroup partials of the
+ * diagnostics, with d_i = logp_i - old_logp_i and r_i = exp(d_i):
+ *   MM_PPO_ST_ENTROPY    sum of H_i
+ *   MM_PPO_ST_KL         sum of expm1(d_i) - d_i (the estimate of KL(old | new))
+ *   MM_PPO_ST_CLIPFRAC   the number of samples with r_i < 1 - clip or r_i > 1 + clip
+ *   MM_PPO_ST_RATIO_MAX  max of r_i
+ * mm_ppo_loss_ent_bwd: dheads [2M, 6] = dloss[0] * (coef * d logp / d heads -
+ * (ent_coef / M) * d H / d heads); d H / d z_j = -p_j (log p_j + H_move) in a
+ * legal move column, -z_5 s (1 - s), s = sigmoid(z_5), in an allowed mark
+ * column, exactly 0 in every masked column and in the move columns of a row
+ * with a single legal move.  ent_coef = 0: the values of mm_ppo_loss_bwd.
+ * mm_ppo_stats_final: out [MM_PPO_STAT_WORDS] f32 = mean entropy, mean KL
+ * estimate, clipped fraction (sums in fp64, fixed order, / M) and the largest
+ * ratio, from the n_partials rows of stat_partial. */
+#define MM_PPO_STAT_WORDS 4
+#define MM_PPO_ST_ENTROPY 0
+#define MM_PPO_ST_KL 1
+#define MM_PPO_ST_CLIPFRAC 2
+#define MM_PPO_ST_RATIO_MAX 3
+int mm_ppo_loss_ent(const float* heads, const uint8_t* masks, const int8_t* actions, const float* old_logp,
+                    const float* adv, int M, float clip, float ent_coef, float* coef, float* partial,
+                    float* stat_partial, void* stream);
+int mm_ppo_loss_ent_bwd(const float* heads, const uint8_t* masks, const int8_t* actions, const float* coef,
+                        const float* dloss, int M, float ent_coef, float* dheads, void* stream);
+int mm_ppo_stats_final(const float* stat_partial, int n_partials, int M, float* out, void* stream);
+
 /* The rest of one update minibatch step (PPO.py:58-85; csrc/update_kernels.hip),
  * so that the step is hand-written launches only.  Sums run in a fixed order.
  *
@@ -483,6 +519,19 @@ int mm_mse_loss_partials(int M);
 int mm_mse_loss(const float* v, const float* rtg, int M, float* dv, float* partial, void* stream);
 int mm_losses_final(const float* ppo_partial, int n_ppo, const float* mse_partial, int n_mse, int M, float* out,
                     void* stream);
+/* Range normalisation of a backward's input gradient (no reference counterpart).
+ * The fp16-plane backward GEMMs scale dY by 2^floor(log2 M), which suits the
+ * gradient of a mean over M rows of O(1) terms; a loss whose per-row terms are
+ * much smaller (an entropy bonus alone: ent_coef / M) would fall into fp16's
+ * subnormals.  A backward is linear and a power of two commutes with rounding.
+ * mm_pow2_norm: out[0] = kappa = 2^k (|k| <= 60) with kappa * max|x| * target
+ * in [1, 2), out[1] = 1 / kappa, for x [n] f32; kappa = 1 when max|x| is 0 or
+ * not finite.  ws: mm_pow2_norm_ws_len() floats.  mm_scale_by: x[i] *=
+ * factor[0], factor a device scalar (kappa before the backward on dz, 1 / kappa
+ * after it on the gradients): no host synchronisation. */
+int mm_pow2_norm_ws_len(void);
+int mm_pow2_norm(const float* x, long n, float target, float* ws, float* out, void* stream);
+int mm_scale_by(float* x, long n, const float* factor, void* stream);
 
 /* clip_grad_norm_(params, max_norm) followed by Adam.step() (PPO.py:74-85),
  * for up to 4 networks ("segments") at once, each over flat f32 buffers of n

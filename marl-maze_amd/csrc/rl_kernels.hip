@@ -29,6 +29,10 @@
 //             gradient of the loss w.r.t. the six head logits of each agent
 //             row directly (torch's min() splits a tie's gradient in half, as
 //             here).
+//   k_ppo_loss_ent / k_ppo_loss_ent_bwd / k_ppo_stats_final  the same with an
+//             entropy bonus (loss = surrogate - ent_coef mean H) and the update's
+//             diagnostics (entropy, KL estimate, clipped fraction, largest
+//             ratio); no reference counterpart, PPO.py:62-79 extended.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -433,6 +437,171 @@ __global__ __launch_bounds__(256) void k_ppo_loss_bwd(const float* __restrict__ 
     for (int j = 0; j < 6; j++) dz[(size_t)r * 6 + j] = c * g[j];
 }
 
+// per agent row: the entropy of the masked move distribution plus that of the mark Bernoulli (where the mark is
+// allowed), with row_logp's mx, e_j and se; also d H / d z when grad != null.  p_j = e_j / se, log p_j =
+// (z_j - mx) - log se; a p_j that underflowed to 0, an illegal column and a row with no legal move give 0.
+//   d H_move / d z_j = -p_j (log p_j + H_move)          (0 for a single legal move: p = 1, log p = 0, H = 0)
+//   H_mark = log1p(t) + a t / (1 + t), a = |z_5|, t = exp(-a);  d H_mark / d z_5 = -z_5 s (1 - s) with
+//   s (1 - s) = t / (1 + t)^2 for s = sigmoid(z_5): no cancellation, and 0 once t underflows
+__device__ __forceinline__ float row_entropy(const float* z, const uint8_t* mk, float* grad) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+        if (mk[j]) mx = fmaxf(mx, z[j]);
+    float se = 0.f;
+    float e[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        e[j] = mk[j] ? expf(z[j] - mx) : 0.f;
+        se += e[j];
+    }
+    const bool any = se > 0.f;  // a legal move exists (its e is 1 at the maximum)
+    const float lse = logf(se);
+    const float inv = 1.f / se;
+    float p[5], lp[5];
+    float hm = 0.f;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        p[j] = any ? e[j] * inv : 0.f;
+        lp[j] = p[j] > 0.f ? (z[j] - mx) - lse : 0.f;
+        hm -= p[j] * lp[j];
+    }
+    float hk = 0.f, t = 0.f, a = 0.f;
+    if (mk[5]) {
+        a = fabsf(z[5]);
+        t = expf(-a);
+        hk = log1pf(t) + a * t / (1.f + t);
+    }
+    if (grad) {
+#pragma unroll
+        for (int j = 0; j < 5; j++) grad[j] = p[j] > 0.f ? -p[j] * (lp[j] + hm) : 0.f;
+        grad[5] = mk[5] ? -z[5] * (t / ((1.f + t) * (1.f + t))) : 0.f;
+    }
+    return hm + hk;
+}
+
+// k_ppo_loss with the update's diagnostics: coef and partial by the same operations in the same order (equal
+// values), and per workgroup the sums of the joint entropy H_i and of expm1(d_i) - d_i (d = logp - old_logp: the
+// KL estimate, >= 0 term by term), the number of samples whose ratio left [1 - clip, 1 + clip] (an integer
+// count, the complement of `inside`) and the largest ratio: stat[block, MM_PPO_ST_*], fixed-order trees
+__global__ __launch_bounds__(kLossThreads) void k_ppo_loss_ent(const float* __restrict__ z,
+                                                               const uint8_t* __restrict__ mk,
+                                                               const int8_t* __restrict__ act,
+                                                               const float* __restrict__ old_lp,
+                                                               const float* __restrict__ adv, int M, float clip,
+                                                               float* __restrict__ coef, float* __restrict__ partial,
+                                                               float* __restrict__ stat) {
+    __shared__ float red[kLossThreads], red_h[kLossThreads], red_kl[kLossThreads], red_mx[kLossThreads];
+    __shared__ int red_n[kLossThreads];
+    const int i = blockIdx.x * kLossThreads + threadIdx.x;
+    float term = 0.f, H = 0.f, kl = 0.f, rmax = -INFINITY;
+    int out = 0;
+    if (i < M) {
+        float lp = 0.f;
+#pragma unroll
+        for (int a = 0; a < 2; a++) {
+            const int r = 2 * i + a;
+            lp += row_logp(z + (size_t)r * 6, mk + (size_t)r * 6, act[2 * r], act[2 * r + 1], nullptr);
+            H += row_entropy(z + (size_t)r * 6, mk + (size_t)r * 6, nullptr);
+        }
+        const float d = lp - old_lp[i];
+        const float ratio = expf(d);
+        const float A = adv[i];
+        const float s1 = ratio * A;
+        const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
+        const float s2 = rc * A;
+        term = fminf(s1, s2);
+        const bool inside = ratio >= 1.f - clip && ratio <= 1.f + clip;
+        float dd;
+        if (s1 < s2) dd = A;
+        else if (s1 > s2) dd = inside ? A : 0.f;
+        else dd = 0.5f * A + (inside ? 0.5f * A : 0.f);
+        coef[i] = -dd * ratio / (float)M;
+        kl = expm1f(d) - d;
+        out = inside ? 0 : 1;
+        rmax = ratio;
+    }
+    red[threadIdx.x] = term;
+    red_h[threadIdx.x] = H;
+    red_kl[threadIdx.x] = kl;
+    red_mx[threadIdx.x] = rmax;
+    red_n[threadIdx.x] = out;
+    __syncthreads();
+    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            red[threadIdx.x] += red[threadIdx.x + w];
+            red_h[threadIdx.x] += red_h[threadIdx.x + w];
+            red_kl[threadIdx.x] += red_kl[threadIdx.x + w];
+            red_mx[threadIdx.x] = fmaxf(red_mx[threadIdx.x], red_mx[threadIdx.x + w]);
+            red_n[threadIdx.x] += red_n[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = red[0];
+        float* st = stat + (size_t)blockIdx.x * MM_PPO_STAT_WORDS;
+        st[MM_PPO_ST_ENTROPY] = red_h[0];
+        st[MM_PPO_ST_KL] = red_kl[0];
+        st[MM_PPO_ST_CLIPFRAC] = (float)red_n[0];  // <= 256: exact
+        st[MM_PPO_ST_RATIO_MAX] = red_mx[0];
+    }
+}
+
+// k_ppo_loss_bwd of surrogate - ent_coef mean_i H_i: dz = (dloss coef) d logp / dz - (dloss ent_coef / M) d H / dz
+// per agent row (ent_m = ent_coef / M; at 0 the values of k_ppo_loss_bwd)
+__global__ __launch_bounds__(256) void k_ppo_loss_ent_bwd(const float* __restrict__ z, const uint8_t* __restrict__ mk,
+                                                          const int8_t* __restrict__ act,
+                                                          const float* __restrict__ coef,
+                                                          const float* __restrict__ dloss, int M, float ent_m,
+                                                          float* __restrict__ dz) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;  // agent row
+    if (r >= 2 * M) return;
+    float g[6], gh[6];
+    row_logp(z + (size_t)r * 6, mk + (size_t)r * 6, act[2 * r], act[2 * r + 1], g);
+    row_entropy(z + (size_t)r * 6, mk + (size_t)r * 6, gh);
+    const float c = coef[r >> 1] * dloss[0];
+    const float ce = ent_m * dloss[0];
+#pragma unroll
+    for (int j = 0; j < 6; j++) dz[(size_t)r * 6 + j] = c * g[j] - ce * gh[j];
+}
+
+// the update's four diagnostics from k_ppo_loss_ent's per-workgroup partials: one workgroup, thread t adds
+// partials t, t + 256, ... in fp64 (ascending), then a fixed-order tree; means are sums / M
+__global__ __launch_bounds__(256) void k_ppo_stats_final(const float* __restrict__ stat, int n, int M,
+                                                         float* __restrict__ out) {
+    __shared__ double rh[256], rk[256], rn[256];
+    __shared__ float rm[256];
+    double h = 0.0, k = 0.0, c = 0.0;
+    float m = -INFINITY;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const float* st = stat + (size_t)j * MM_PPO_STAT_WORDS;
+        h += (double)st[MM_PPO_ST_ENTROPY];
+        k += (double)st[MM_PPO_ST_KL];
+        c += (double)st[MM_PPO_ST_CLIPFRAC];
+        m = fmaxf(m, st[MM_PPO_ST_RATIO_MAX]);
+    }
+    rh[threadIdx.x] = h;
+    rk[threadIdx.x] = k;
+    rn[threadIdx.x] = c;
+    rm[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            rh[threadIdx.x] += rh[threadIdx.x + w];
+            rk[threadIdx.x] += rk[threadIdx.x + w];
+            rn[threadIdx.x] += rn[threadIdx.x + w];
+            rm[threadIdx.x] = fmaxf(rm[threadIdx.x], rm[threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[MM_PPO_ST_ENTROPY] = (float)(rh[0] / (double)M);
+        out[MM_PPO_ST_KL] = (float)(rk[0] / (double)M);
+        out[MM_PPO_ST_CLIPFRAC] = (float)(rn[0] / (double)M);
+        out[MM_PPO_ST_RATIO_MAX] = rm[0];
+    }
+}
+
 
 // ---------------------------------------------------------------------------
 // The critic's value, fused (networks.py:87-102 forward, inference only): V = w2 . ReLU(W1 ReLU(W0 x + b0) + b1)
@@ -685,6 +854,34 @@ extern "C" int mm_ppo_loss_bwd(const float* heads, const uint8_t* masks, const i
     if (!heads || !masks || !actions || !coef || !dloss || !dheads || M <= 0) return MM_E_ARG;
     hipLaunchKernelGGL(k_ppo_loss_bwd, dim3((2 * M + 255) / 256), dim3(256), 0, (hipStream_t)stream, heads, masks,
                        actions, coef, dloss, M, dheads);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_ppo_loss_ent(const float* heads, const uint8_t* masks, const int8_t* actions, const float* old_logp,
+                               const float* adv, int M, float clip, float ent_coef, float* coef, float* partial,
+                               float* stat_partial, void* stream) {
+    if (!heads || !masks || !actions || !old_logp || !adv || !coef || !partial || !stat_partial || M <= 0 ||
+        !(ent_coef == ent_coef))
+        return MM_E_ARG;
+    // (the forward's outputs do not depend on ent_coef: partial is the surrogate alone, the bonus enters the backward)
+    hipLaunchKernelGGL(k_ppo_loss_ent, dim3(mm_ppo_loss_partials(M)), dim3(kLossThreads), 0, (hipStream_t)stream,
+                       heads, masks, actions, old_logp, adv, M, clip, coef, partial, stat_partial);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_ppo_loss_ent_bwd(const float* heads, const uint8_t* masks, const int8_t* actions, const float* coef,
+                                   const float* dloss, int M, float ent_coef, float* dheads, void* stream) {
+    if (!heads || !masks || !actions || !coef || !dloss || !dheads || M <= 0 || !(ent_coef == ent_coef))
+        return MM_E_ARG;
+    hipLaunchKernelGGL(k_ppo_loss_ent_bwd, dim3((2 * M + 255) / 256), dim3(256), 0, (hipStream_t)stream, heads, masks,
+                       actions, coef, dloss, M, ent_coef / (float)M, dheads);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_ppo_stats_final(const float* stat_partial, int n_partials, int M, float* out, void* stream) {
+    if (!stat_partial || !out || n_partials <= 0 || M <= 0) return MM_E_ARG;
+    hipLaunchKernelGGL(k_ppo_stats_final, dim3(1), dim3(256), 0, (hipStream_t)stream, stat_partial, n_partials, M,
+                       out);
     return (int)hipGetLastError();
 }
 

@@ -8,6 +8,9 @@
 //   mm_mse_loss     the critic loss nn.MSELoss()(V, rtg) (PPO.py:78-80): per-
 //                   workgroup partial sums of (V - rtg)^2 and dV = 2 (V - rtg) / M
 //   mm_losses_final the two losses from the partial sums: [actor, critic]
+//   mm_pow2_norm / mm_scale_by  a power-of-two range normalisation of the actor's
+//                   dz before its backward and of its gradients after it (used
+//                   with an entropy bonus: its gradient is far below 1 / M)
 //   mm_clip_adam    clip_grad_norm_(params, max_grad) + Adam.step() per network
 //                   (PPO.py:74-85) over flat parameter / gradient / moment buffers
 //
@@ -94,6 +97,62 @@ __global__ __launch_bounds__(256) void k_losses_final(const float* __restrict__ 
         out[0] = -a / (float)M;
         out[1] = c / (float)M;
     }
+}
+
+// ---- range normalisation of a backward's input gradient (mm_pow2_norm, mm_scale_by) ----
+// The fp16-plane backward GEMMs scale dY by 2^floor(log2 M): built for gradients of a mean over M rows whose
+// per-row terms are O(1).  A loss term with a small weight (the entropy bonus alone is ent_coef / M per row)
+// falls below that, into fp16's subnormals.  A backward is linear in dz, and a power of two commutes with every
+// rounding: dz is multiplied by kappa = 2^k so that its largest entry is where the GEMMs expect it, and the
+// gradients by 1 / kappa -- all on the device.
+constexpr int kAbsmaxBlocks = 256;
+
+// max |x[i]| per workgroup (grid-stride, fixed tree); NaN entries are ignored by fmaxf
+__global__ __launch_bounds__(256) void k_absmax_partial(const float* __restrict__ x, long n,
+                                                        float* __restrict__ part) {
+    __shared__ float red[256];
+    float m = 0.f;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// out[0] = kappa = 2^k with kappa * max * target in [1, 2), out[1] = 1 / kappa; |k| <= 60 (both exact and far
+// from fp32's limits); max == 0 or not finite: kappa = 1
+__global__ __launch_bounds__(256) void k_pow2_final(const float* __restrict__ part, int np, float target,
+                                                    float* __restrict__ out) {
+    __shared__ float red[256];
+    float m = 0.f;
+    for (int j = threadIdx.x; j < np; j += 256) m = fmaxf(m, part[j]);
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float v = red[0] * target;
+        int k = 0;
+        if (v > 0.f && v <= 3.0e38f) {
+            int e;
+            frexpf(v, &e);  // v = f 2^e, f in [0.5, 1)
+            k = 1 - e;
+            k = k < -60 ? -60 : (k > 60 ? 60 : k);
+        }
+        out[0] = ldexpf(1.f, k);
+        out[1] = ldexpf(1.f, -k);
+    }
+}
+
+// x[i] *= factor[0] (a device scalar)
+__global__ __launch_bounds__(256) void k_scale_by(float* __restrict__ x, long n, const float* __restrict__ factor) {
+    const float f = factor[0];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= f;
 }
 
 // ---- clip_grad_norm_ + Adam ----
@@ -370,6 +429,28 @@ extern "C" int mm_losses_final(const float* ppo_partial, int n_ppo, const float*
     if (!ppo_partial || !mse_partial || !out || n_ppo <= 0 || n_mse <= 0 || M <= 0) return MM_E_ARG;
     hipLaunchKernelGGL(k_losses_final, dim3(1), dim3(256), 0, (hipStream_t)stream, ppo_partial, n_ppo, mse_partial,
                        n_mse, M, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_pow2_norm_ws_len(void) { return kAbsmaxBlocks; }
+
+extern "C" int mm_pow2_norm(const float* x, long n, float target, float* ws, float* out, void* stream) {
+    if (!x || !ws || !out || n <= 0 || !(target > 0.f)) return MM_E_ARG;
+    long blocks = (n + 1023) / 1024;  // about 4 elements per thread
+    if (blocks > kAbsmaxBlocks) blocks = kAbsmaxBlocks;
+    hipLaunchKernelGGL(k_absmax_partial, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, ws);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_pow2_final, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (int)blocks,
+                       target, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mm_scale_by(float* x, long n, const float* factor, void* stream) {
+    if (!x || !factor || n <= 0) return MM_E_ARG;
+    long blocks = (n + 1023) / 1024;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_scale_by, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, factor);
     return (int)hipGetLastError();
 }
 

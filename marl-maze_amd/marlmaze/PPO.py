@@ -71,6 +71,31 @@ def _ppo_loss_bwd(heads, mk, a8, coef, dloss):
     return dz
 
 
+def _ppo_loss_ent_fwd(heads, mk, a8, old_logp, adv, clip, ent_coef):
+    """mm_ppo_loss_ent: (coef, partial) as _ppo_loss_fwd, and the diagnostics' per-workgroup partials
+    [partials, PPO_STAT_WORDS] for update.ppo_stats_final."""
+    L = _lib.lib()
+    M = old_logp.shape[0]
+    old_logp, adv = old_logp.contiguous(), adv.contiguous()
+    coef = torch.empty(M, dtype=torch.float32, device=heads.device)
+    n = L.mm_ppo_loss_partials(M)
+    part = torch.empty(n, dtype=torch.float32, device=heads.device)
+    stat_part = torch.empty((n, _lib.PPO_STAT_WORDS), dtype=torch.float32, device=heads.device)
+    _lib.check(L.mm_ppo_loss_ent(_lib.ptr(heads), _lib.ptr(mk), _lib.ptr(a8), _lib.ptr(old_logp), _lib.ptr(adv), M,
+                                 float(clip), float(ent_coef), _lib.ptr(coef), _lib.ptr(part), _lib.ptr(stat_part),
+                                 _lib.stream_ptr()), "mm_ppo_loss_ent")
+    return coef, part, stat_part
+
+
+def _ppo_loss_ent_bwd(heads, mk, a8, coef, dloss, ent_coef):
+    """mm_ppo_loss_ent_bwd: d (surrogate - ent_coef mean H) / d heads [2M, 6]."""
+    dz = torch.empty_like(heads)
+    _lib.check(_lib.lib().mm_ppo_loss_ent_bwd(_lib.ptr(heads), _lib.ptr(mk), _lib.ptr(a8), _lib.ptr(coef),
+                                              _lib.ptr(dloss), coef.shape[0], float(ent_coef), _lib.ptr(dz),
+                                              _lib.stream_ptr()), "mm_ppo_loss_ent_bwd")
+    return dz
+
+
 def _u8(masks):
     masks = masks.contiguous()
     return masks.view(torch.uint8) if masks.dtype == torch.bool else masks.to(torch.uint8)
@@ -103,7 +128,7 @@ class PPO:
                  updates_per_batch=5, clip=0.2, max_grad=0.5, *, n_envs=4096, horizon=None, env_config=None,
                  seed=3234, sample_seed=None, device=None, model_path=MODEL_PATH, load=True, parity_mode=True,
                  bootstrap=True, dp=None, verbose=True, save=True, episode_batches=False,
-                 episode_chunk=64, dtype="f32", graph_rollout=False):
+                 episode_chunk=64, dtype="f32", graph_rollout=False, ent_coef=0.0, diagnostics=False):
         self.maze = None  # wired by Maze.__init__ (maze.py:39-42), as in the reference
         self.dp = dp if dp is not None else DP.single()
         if device is None:
@@ -158,6 +183,15 @@ class PPO:
         self.mbatch_size = self.batch_size // 5
         self.clip = clip
         self.max_grad = max_grad
+        # entropy bonus (no reference counterpart): the update minimises surrogate - ent_coef * mean joint entropy
+        # of the masked move distributions and the mark Bernoullis.  With a bonus, or with ``diagnostics``, every
+        # minibatch also yields [entropy, approx_kl, clip_frac, ratio_max] (``last_update_stats`` [K, 4]); with
+        # neither (the default) the update is the reference's, launch for launch.  Not part of the checkpoint
+        self.ent_coef = float(ent_coef)
+        if not math.isfinite(self.ent_coef):
+            raise ValueError(f"ent_coef must be finite, not {ent_coef!r}")
+        self.diagnostics = bool(diagnostics)
+        self.last_update_stats = None
 
         self.n_envs = int(n_envs)
         self.horizon = int(horizon) if horizon else max(1, math.ceil(batch_size / (self.n_envs * self.dp.world)))
@@ -253,10 +287,19 @@ class PPO:
         lp = (lp + torch.log(p)).view(M, 2)
         return lp[:, 0] + lp[:, 1]
 
-    def minibatch_grads(self, obs, act, old_logp, adv, rtg, masks, out=None):
+    @property
+    def stats_on(self):
+        """The update runs the entropy form of the policy loss and fills ``last_update_stats``."""
+        return self.diagnostics or self.ent_coef != 0.0
+
+    def minibatch_grads(self, obs, act, old_logp, adv, rtg, masks, out=None, stats_out=None):
         """Losses of PPO.py:62-80 and their gradients in every parameter's .grad
         (before the all-reduce, the clipping and Adam).  Returns (actor_loss,
         critic_loss) as 0-dim tensors (views of ``out`` [2] when given).
+        The actor loss is the clipped surrogate, also with an entropy bonus (whose
+        gradient is in .grad): comparable with the reference's.  With ``stats_on``,
+        ``stats_out`` [4] (optional) receives [entropy, approx_kl, clip_frac,
+        ratio_max] of this minibatch.
 
         On the GPU: no autograd.  The critic and actor forwards keep what their
         backwards need; the policy loss (mm_ppo_loss) and the value loss
@@ -264,7 +307,7 @@ class PPO:
         explicit backwards (Actor / Critic .train_backward), which write into the
         flat gradient buffer."""
         if not obs.is_cuda:
-            return self._minibatch_grads_host(obs, act, old_logp, adv, rtg, masks)
+            return self._minibatch_grads_host(obs, act, old_logp, adv, rtg, masks, stats_out)
         M = obs.shape[0]
         a8 = (act if act.dtype == torch.int8 else act.to(torch.int8)).contiguous()
         mk = _u8(masks)
@@ -288,41 +331,82 @@ class PPO:
                     with x3.deferred():
                         self.critic.train_backward(csaved, dv)
             heads, asaved = self.actor.train_forward(obs.reshape(2 * M, 65))
-            coef, ppo_part = _ppo_loss_fwd(heads, mk, a8, old_logp, adv, self.clip)
-            dz = _ppo_loss_bwd(heads, mk, a8, coef, self._one)
+            kappa = None
+            if self.stats_on:  # the same loss with the entropy bonus in dz, and the diagnostics' partial sums
+                coef, ppo_part, stat_part = _ppo_loss_ent_fwd(heads, mk, a8, old_logp, adv, self.clip, self.ent_coef)
+                dz = _ppo_loss_ent_bwd(heads, mk, a8, coef, self._one, self.ent_coef)
+                if self.ent_coef != 0.0 and self.gemm_prec != "x3":
+                    # the fp16-plane backward GEMMs expect max |dz| of a few / M (a mean of O(1) terms); where the
+                    # bonus carries the gradient it is ent_coef times that, into fp16's subnormals.  dz times a
+                    # power of two, the actor's gradients divided by it again: exact, on the device
+                    kappa = update.pow2_norm(dz, M / 4.0)  # kappa max|dz| in [4 / M, 8 / M)
+                    update.scale_by(dz, kappa[0:1])
+            else:
+                coef, ppo_part = _ppo_loss_fwd(heads, mk, a8, old_logp, adv, self.clip)
+                dz = _ppo_loss_bwd(heads, mk, a8, coef, self._one)
             with x3.deferred():
                 self.actor.train_backward(asaved, dz)
+            if kappa is not None:
+                update.scale_by(self.flat.seg_view(self.flat.grad, 0), kappa[1:2])
             critic_side.join(mse_part)
             update.losses_final(ppo_part, mse_part, M, out)
+            if self.stats_on and stats_out is not None:
+                update.ppo_stats_final(stat_part, M, stats_out)
         return out[0], out[1]
 
-    def _minibatch_grads_host(self, obs, act, old_logp, adv, rtg, masks):
-        """The CPU torch form (autograd, the reference's formulas)."""
+    def policy_entropy(self, obs, masks):
+        """The joint entropy [M] of the policy at ``obs``: per agent the masked move Categorical's plus, where the
+        mark is allowed, the mark Bernoulli's (torch.distributions; a row with no legal move counts 0)."""
+        M = obs.shape[0]
+        ml, kl = self.actor(obs.reshape(2 * M, 65))
+        mk = masks.reshape(2 * M, 6).bool()
+        legal = mk[:, 0:5].any(1)
+        mv = mk[:, 0:5] | ~legal[:, None]  # (a row with no legal move: any finite distribution, then times 0)
+        h_move = torch.distributions.Categorical(logits=ml.masked_fill(~mv, float("-inf"))).entropy() * legal
+        kl = torch.where(mk[:, 5], kl.squeeze(1), torch.zeros_like(kl.squeeze(1)))
+        h_mark = torch.distributions.Bernoulli(logits=kl).entropy() * mk[:, 5]
+        return (h_move + h_mark).view(M, 2).sum(1)
+
+    def _minibatch_grads_host(self, obs, act, old_logp, adv, rtg, masks, stats_out=None):
+        """The CPU torch form (autograd, the reference's formulas; the entropy bonus and the diagnostics with
+        torch.distributions)."""
         V = self.critic(obs).view(-1)
         cur = self.policy_logp(obs, act, masks)
-        ratio = torch.exp(cur - old_logp)
+        d = cur - old_logp
+        ratio = torch.exp(d)
         s1 = ratio * adv
         s2 = torch.clamp(ratio, 1 - self.clip, 1 + self.clip) * adv
         actor_loss = -torch.mean(torch.min(s1, s2))
         critic_loss = torch.nn.functional.mse_loss(V, rtg)
+        total = actor_loss + critic_loss
+        if self.stats_on:
+            entropy = self.policy_entropy(obs, masks).mean()
+            if self.ent_coef != 0.0:
+                total = total - self.ent_coef * entropy
+            if stats_out is not None:
+                with torch.no_grad():
+                    outside = (ratio < 1 - self.clip) | (ratio > 1 + self.clip)
+                    stats_out.copy_(torch.stack([entropy.detach(), (torch.expm1(d) - d).mean(),
+                                                 outside.to(ratio.dtype).mean(), ratio.max()]))
         self.actor_optim.zero_grad(set_to_none=True)
         self.critic_optim.zero_grad(set_to_none=True)
-        (actor_loss + critic_loss).backward()  # disjoint parameters: same grads as two backwards
+        total.backward()  # disjoint parameters: same grads as two backwards
         return actor_loss.detach(), critic_loss.detach()
 
-    def minibatch_step(self, obs, act, old_logp, adv, rtg, masks, out=None):
+    def minibatch_step(self, obs, act, old_logp, adv, rtg, masks, out=None, stats_out=None):
         """One iteration of PPO.py:58-85: losses, gradients, all-reduce (DP),
         clip_grad_norm_ per network, Adam.  Returns (aloss, closs, gnorm_a,
         gnorm_c) as 0-dim tensors (views of ``out`` [4] when given).
+        ``stats_out``: as minibatch_grads.
 
         On the GPU the step is the minibatch_grads launches, one all-reduce of the
         flat gradient buffer under DP (sums; the 1 / world scale is folded into
         the optimizer kernel), and mm_clip_adam for both networks."""
         if self.flat is None:
-            return self._minibatch_step_host(obs, act, old_logp, adv, rtg, masks)
+            return self._minibatch_step_host(obs, act, old_logp, adv, rtg, masks, stats_out)
         if out is None:
             out = torch.empty(4, dtype=torch.float32, device=obs.device)
-        self.minibatch_grads(obs, act, old_logp, adv, rtg, masks, out=out[0:2])
+        self.minibatch_grads(obs, act, old_logp, adv, rtg, masks, out=out[0:2], stats_out=stats_out)
         scale = 1.0
         if self.dp.active:
             self.dp.allreduce_sum(self.flat.grad)
@@ -330,8 +414,8 @@ class PPO:
         update.clip_adam([self.actor_optim, self.critic_optim], self.max_grad, norms=out[2:4], grad_scale=scale)
         return out[0], out[1], out[2], out[3]
 
-    def _minibatch_step_host(self, obs, act, old_logp, adv, rtg, masks):
-        actor_loss, critic_loss = self._minibatch_grads_host(obs, act, old_logp, adv, rtg, masks)
+    def _minibatch_step_host(self, obs, act, old_logp, adv, rtg, masks, stats_out=None):
+        actor_loss, critic_loss = self._minibatch_grads_host(obs, act, old_logp, adv, rtg, masks, stats_out)
         params = list(self.actor.parameters()) + list(self.critic.parameters())
         self.dp.allreduce_grads(params)
         gna = torch.nn.utils.clip_grad_norm_(self.actor.parameters(), self.max_grad)
@@ -380,17 +464,26 @@ class PPO:
 
         def passes():
             hist = torch.empty((K, 4), dtype=torch.float32, device=b_obs.device)
+            stats = None
+            if self.stats_on:  # [entropy, approx_kl, clip_frac, ratio_max] per minibatch (a redo's replace the first's)
+                stats = self.last_update_stats = torch.empty((K, _lib.PPO_STAT_WORDS), dtype=torch.float32,
+                                                             device=b_obs.device)
             k = 0
             for _ in range(self.updates_per_batch):
                 self.decay_lr()
                 for args in mbs:
-                    row = self.minibatch_step(*args, **({"out": hist[k]} if self.flat is not None else {}))
+                    kw = {"out": hist[k]} if self.flat is not None else {}
+                    if stats is not None:
+                        kw["stats_out"] = stats[k]
+                    row = self.minibatch_step(*args, **kw)
                     if self.flat is None:
                         hist[k] = torch.stack(row)
                     k += 1
             if self.dp.active:  # local losses -> global-minibatch losses (equal shards); norms are already global
                 self.dp.allreduce_sum(hist)
                 hist /= self.dp.world
+                if stats is not None:
+                    self.dp.allreduce_update_stats(stats)
             return hist
 
         self.last_update_discarded = False
@@ -436,6 +529,8 @@ class PPO:
             self.range_switched = True
             self.batches_discarded += 1
             hist.fill_(float("nan"))
+            if self.last_update_stats is not None:
+                self.last_update_stats.fill_(float("nan"))
             return hist
         if post_set:
             snap.restore()
@@ -474,12 +569,17 @@ class PPO:
             episodes, mean_len, mean_short = self.dp.episode_stats(ep_lens, b_sp)  # all ranks' episodes
             stats = dict(epoch=epoch, episodes=episodes, mean_len=mean_len, mean_shortest=mean_short,
                          actor_loss=float(hist[-1, 0]), critic_loss=float(hist[-1, 1]))
+            if self.stats_on:  # the last minibatch's, as the losses
+                stats.update(zip(_lib.PPO_STAT_FIELDS, self.last_update_stats[-1].tolist()))
             self.history.append(stats)
             if self.verbose:  # PPO.py:37-44, condensed
                 print(f"-------------------- Epoch #{epoch} --------------------")
                 print(f"Mazes solved in current epoch: {stats['episodes']}")
                 print(f"Average Exit Time: {stats['mean_len']}")
                 print(f"Average Length of Shortest Path: {stats['mean_shortest']}", flush=True)
+                if self.stats_on:
+                    print(f"Policy entropy: {stats['entropy']:.4f}  approx KL: {stats['approx_kl']:.3g}  clipped: "
+                          f"{stats['clip_frac']:.3f}  max ratio: {stats['ratio_max']:.3f}", flush=True)
             if eval_every > 0 and (epoch + 1) % eval_every == 0:
                 from .evaluate import format_result
 

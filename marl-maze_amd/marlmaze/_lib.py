@@ -71,8 +71,14 @@ EXPORTS = ("mm_version", "mm_env_desc_size", "mm_layout_stride", "mm_env_seed", 
            "mm_env_dist", "mm_env_par", "mm_par_init", "mm_par_accum",
            "mm_elog_state_words", "mm_elog_init", "mm_elog_start", "mm_elog_step",
            "mm_gemm_x2p_ok", "mm_gemm_x2p_dy_ok", "mm_x3_heads_bwd_x2p",
-           "mm_critic_update_ok", "mm_critic_update")
+           "mm_critic_update_ok", "mm_critic_update",
+           "mm_ppo_loss_ent", "mm_ppo_loss_ent_bwd", "mm_ppo_stats_final",
+           "mm_pow2_norm_ws_len", "mm_pow2_norm", "mm_scale_by")
 VERSION = 308  # mm_version() this binding is written for
+
+PPO_STAT_WORDS = 4  # MM_PPO_STAT_WORDS: f32 words of an update's diagnostics (mm_ppo_loss_ent, mm_ppo_stats_final)
+PPO_ST_ENTROPY, PPO_ST_KL, PPO_ST_CLIPFRAC, PPO_ST_RATIO_MAX = 0, 1, 2, 3  # MM_PPO_ST_*
+PPO_STAT_FIELDS = ("entropy", "approx_kl", "clip_frac", "ratio_max")  # the history keys, in word order
 
 PREC_X3, PREC_F16, PREC_X2 = 0, 1, 2  # MM_PREC_*
 FRONT_BWD = {"mfma": 0, "valu": 1}  # MM_FRONT_BWD_*
@@ -290,6 +296,12 @@ def lib():
                            ("mm_x3_heads_bwd_x2p", [P, i32, P, P, i32, i32, P, P, f32, P]),
                            ("mm_critic_update_ok", [i32, i32, i32]),
                            ("mm_critic_update", [P, i32, i32, i32] + [P] * 18),
+                           ("mm_ppo_loss_ent", [P, P, P, P, P, i32, f32, f32, P, P, P, P]),
+                           ("mm_ppo_loss_ent_bwd", [P, P, P, P, P, i32, f32, P, P]),
+                           ("mm_ppo_stats_final", [P, i32, i32, P, P]),
+                           ("mm_pow2_norm_ws_len", []),
+                           ("mm_pow2_norm", [P, ctypes.c_long, f32, P, P, P]),
+                           ("mm_scale_by", [P, ctypes.c_long, P, P]),
                            ("mm_trunk3_head_sample", [i32, P, i32, i32, i32, P, P, i32, P, P, i32, P, P, i32, P, P, P,
                                                       u64, u64, P, P, P, P, P, P, i32, P])):
             if hasattr(L, name):

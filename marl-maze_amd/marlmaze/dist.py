@@ -15,7 +15,10 @@ independent, so rollout and GAE need no communication; the exchange steps are
    paths: three fp64 sums, ``episode_stats``);
 4. the x2 / f16 range guard's two flags per update (``allreduce_max``), so the
    decision to redo an update at x3, or to discard a batch, is the same on
-   every rank.
+   every rank;
+5. with an entropy bonus or diagnostics, the update's [K, 4] statistics once
+   per update (``allreduce_update_stats``: means as sums / world, the largest
+   ratio as a MAX).
 
 Backend "nccl" is RCCL on ROCm (xGMI inside the node); "gloo" for CPU tests.
 """
@@ -133,6 +136,18 @@ class DP:
         if self.active:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t
+
+    def allreduce_update_stats(self, stats):
+        """In place: every rank's [K, 4] update diagnostics (entropy, approx_kl, clip_frac, ratio_max per
+        minibatch) -> the global minibatches': the three means are sum / world (equal shards), ratio_max is the
+        maximum over ranks."""
+        if self.active:
+            top = stats[:, 3].contiguous()
+            dist.all_reduce(top, op=dist.ReduceOp.MAX)
+            dist.all_reduce(stats, op=dist.ReduceOp.SUM)
+            stats /= self.world
+            stats[:, 3] = top
+        return stats
 
     def raised_on_any_rank(self, *flags):
         """This rank's one-element device flags -> a tuple of ints, each the flag's MAX over ranks: one

@@ -245,3 +245,32 @@ def losses_final(ppo_part, mse_part, M, out):
                                           mse_part.numel(), int(M), _lib.ptr(out), _lib.stream_ptr()),
                "mm_losses_final")
     return out
+
+
+def pow2_norm(x, target):
+    """[kappa, 1 / kappa] on the device: the power of two with kappa * max|x| * target in [1, 2) (mm_pow2_norm;
+    1 when max|x| is 0 or not finite).  No host synchronisation."""
+    L = _lib.lib()
+    x = x.reshape(-1)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    out = torch.empty(2, dtype=torch.float32, device=x.device)
+    ws = torch.empty(L.mm_pow2_norm_ws_len(), dtype=torch.float32, device=x.device)
+    _lib.check(L.mm_pow2_norm(_lib.ptr(x), x.numel(), float(target), _lib.ptr(ws), _lib.ptr(out), _lib.stream_ptr()),
+               "mm_pow2_norm")
+    return out
+
+
+def scale_by(x, factor):
+    """In place: x *= factor[0], factor a one-element device tensor (mm_scale_by)."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and factor.dtype == torch.float32 and factor.numel() == 1
+    _lib.check(_lib.lib().mm_scale_by(_lib.ptr(x), x.numel(), _lib.ptr(factor), _lib.stream_ptr()), "mm_scale_by")
+    return x
+
+
+def ppo_stats_final(stat_part, M, out):
+    """out [PPO_STAT_WORDS] = [entropy, approx_kl, clip_frac, ratio_max] of a minibatch from mm_ppo_loss_ent's
+    per-workgroup partials (mm_ppo_stats_final); ``out`` may be a row of a larger tensor."""
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == _lib.PPO_STAT_WORDS
+    _lib.check(_lib.lib().mm_ppo_stats_final(_lib.ptr(stat_part), stat_part.shape[0], int(M), _lib.ptr(out),
+                                             _lib.stream_ptr()), "mm_ppo_stats_final")
+    return out
